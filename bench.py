@@ -23,6 +23,14 @@ One process per GPU.  `python bench.py --gpus N` without WORLD_SIZE in the envir
 itself (a child `python -m torch.distributed.run ... bench.py <same arguments>`, before this process touches the
 GPU) and relays rank 0's line and the child's exit code; under torch.distributed.run it is a rank.  Rank 0 prints
 ONE JSON line ("Measurement").
+
+A plain run sets up, warms up, times --steps steps and prints the line (headline value, ms_per_step, the roofline of
+the timed steps).  --full adds what is measured or checked besides the headline, outside the timed region: the
+per-kernel stage times, the packed and fixed-length hand-overs, the PCIe-inclusive rate, the stress rows, the pack
+sweep, the oracle parity check and the CPU baseline (each can still be left out with its --no-* switch).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64): the hit records a caller of
+the path receives (read_id, n, then seq_start / seq_end / position / contig of both matches), their count and a seeded
+sample of the per-read counts; at most 64 MB in all (a seeded sample of the rows beyond that).
 """
 import argparse
 import json
@@ -129,6 +137,56 @@ def traffic_entry(shape: str, n: int, L: int):
         return None
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: everything written, at most
+DUMP_COUNTS_READS = 1 << 20    # per-read counts: a seeded sample of at most this many reads
+DUMP_SEED = 20240115
+
+
+def hit_columns(hits):
+    """gf_hit records (int64[k, 6] on the device) -> float64[k, 10]: read_id, n, then seq_start, seq_end, position,
+    contig of m[0] and of m[1] (all exact in float64)."""
+    import numpy as np
+    from genefuserust_amd._lib import HIT_DTYPE
+    rec = np.ascontiguousarray(hits.cpu().numpy()).view(HIT_DTYPE).reshape(-1)
+    cols = [rec["read_id"], rec["n"]]
+    for j in range(2):
+        m = rec["m"][:, j]
+        cols += [m["seq_start"], m["seq_end"], m["position"], m["contig"]]
+    return np.stack([c.astype(np.float64) for c in cols], axis=1).reshape(-1, 10)
+
+
+def dump_outputs(dirname, hit_lists, counts=None):
+    """--dump-outputs: DIR/<name>.npy for every (name, float64 rows) of hit_lists, DIR/n_hits.npy = their lengths, and
+    with `counts` (the step's per-read counts, uint8 on the device) DIR/counts_sample.npy at the read indices
+    of DIR/counts_sample_ids.npy.  A list longer than its share of DUMP_BYTES keeps a seeded sample of its rows, whose
+    indices go to DIR/<name>_rows.npy.  Same inputs, same files."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES - (1 << 20)   # (headers, n_hits)
+    if counts is not None:
+        n = int(counts.numel())
+        if n <= DUMP_COUNTS_READS:
+            ids = np.arange(n, dtype=np.int64)
+        else:
+            ids = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_COUNTS_READS))
+        c = counts[torch.from_numpy(ids).to(counts.device)].cpu().numpy().astype(np.float64)
+        np.save(os.path.join(dirname, "counts_sample.npy"), c)
+        np.save(os.path.join(dirname, "counts_sample_ids.npy"), ids.astype(np.float64))
+        budget -= c.nbytes + 8 * ids.size
+    share = budget // max(len(hit_lists), 1)
+    totals = []
+    for k, (name, a) in enumerate(hit_lists):
+        totals.append(a.shape[0])
+        cap = share // (a.shape[1] * 8 + 8)   # (a row and its index)
+        if a.shape[0] > cap:
+            rows = np.unique(np.random.default_rng(DUMP_SEED + 1 + k).integers(0, a.shape[0], cap))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    np.save(os.path.join(dirname, "n_hits.npy"), np.array(totals, dtype=np.float64))
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` run plainly: start the N ranks as a CHILD torch.distributed.run (this process has not
     initialised the GPU and never will), let rank 0's JSON line through on our stdout, return the child's exit code."""
@@ -174,11 +232,20 @@ def main() -> None:
     ap.add_argument("--calib", action="store_true", help="after the timed steps, launch the counter-calibration kernels of "
                     "tools/gf_calib.hip on the batch's own bases (known byte counts in the same rocprofv3 pass)")
     ap.add_argument("--variant", type=int, default=0, help="first pass: 0 flat pipeline (default), 1 wave-per-read probe-all, 2 wave-per-read seed+verify")
+    ap.add_argument("--full", action="store_true", help="also the extras outside the timed region: stage times, packed / "
+                    "fixed-length hand-overs, PCIe-inclusive rate, stress rows, pack sweep, parity, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))   # (nothing has touched the GPU yet)
-    if args.profile_mode:
+    if args.profile_mode or not args.full:
         args.no_cpu_baseline = args.no_parity = args.no_h2d = args.no_pack_sweep = args.no_stress = True
+    extras = args.full and not args.profile_mode   # the per-stage, packed and fixed-length figures
     cfg = dict(CONFIGS[args.config])
     if args.shape:
         cfg["shape"] = args.shape
@@ -363,6 +430,14 @@ def main() -> None:
     elapsed = float(t.item())
     kern_ms = [a.elapsed_time(b) for a, b in evs]
     kern_ms_avg = sum(kern_ms) / len(kern_ms)
+    if args.dump_outputs and rank == 0:   # the last step's hit list, before anything else runs on these buffers
+        if world == 1:
+            last_hits = out[0][: int(out[1].item())]
+        elif isinstance(out, tuple):      # RcclHitExchange: (merged, totals = [records, overflow flag, ..])
+            last_hits = out[0][: int(out[1][0].item())]
+        else:
+            last_hits = out
+        dump_outputs(args.dump_outputs, [("hits", hit_columns(last_hits))], counts)
     if args.calib and rank == 0:   # outside the timed region: known-byte-count kernels for the PMC passes
         import ctypes
         cal = ctypes.CDLL(os.path.join(ROOT, "tools", "libgfcalib.so"))
@@ -377,7 +452,7 @@ def main() -> None:
     # per-kernel durations of the flat pipeline (HIP events inside the library, launch stream),
     # taken on extra steps outside the timed region
     stage_ms = None
-    if args.variant == 0 and not args.profile_mode:
+    if args.variant == 0 and extras:
         ix.set_profiling(True)
         acc = [0.0, 0.0, 0.0, 0.0]
         reps = 5
@@ -392,7 +467,7 @@ def main() -> None:
     # the packed hand-over (gf_map_reads_packed_device), outside the timed region: the same reads in the
     # kernels' own 2-bit form — what a device-side producer or a host that maps a read set repeatedly hands over
     packed_ms = None
-    if args.variant == 0 and rank == 0 and not args.profile_mode:
+    if args.variant == 0 and rank == 0 and extras:
         t_ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         t_ev[0].record(stream)
         pk, iv = ix.pack_bases_device(reads.bases)
@@ -413,7 +488,7 @@ def main() -> None:
     # the fixed-length hand-over (gf_map_reads_fixed_device), outside the timed region: the same reads without the
     # int64 offsets array — every read of the batch has L bases, the kernels compute where it starts
     fixed_ms = None
-    if args.variant == 0 and rank == 0 and not args.profile_mode and L <= 320:
+    if args.variant == 0 and rank == 0 and extras and L <= 320:
         c3 = torch.empty_like(counts)
         m3 = torch.empty_like(matches)
         ix.map_reads_fixed_device(reads.bases, L, c3, m3)
@@ -855,7 +930,7 @@ def bench_multi_csv(args, cfg, world, rank, local_rank, dev, barrier, seed, gene
             ns = min(j.hi - j.lo, 200_000)
             kept[j.csv] = (torch.empty(ns, dtype=torch.uint8, device=dev), torch.empty((ns, 2, 4), dtype=torch.int32, device=dev))
 
-    def step(record):
+    def step(record, keep=None):
         packed = None   # once per step: the reads' 2-bit form, shared by all the CSVs of the step
         for j in jobs:
             gs = sets[j.csv]
@@ -880,6 +955,8 @@ def bench_multi_csv(args, cfg, world, rank, local_rank, dev, barrier, seed, gene
                 k = merged.shape[0]
             else:
                 k = int(n_hits.item())   # (waits for the launches)
+            if keep is not None:   # --dump-outputs, last timed step: this CSV's hit list as its caller receives it
+                keep[j.csv] = merged if len(j.group) > 1 else hits[:k].clone()
             torch.cuda.synchronize()
             t2 = time.perf_counter()
             if record:
@@ -896,15 +973,18 @@ def bench_multi_csv(args, cfg, world, rank, local_rank, dev, barrier, seed, gene
     for _ in range(args.warmup):
         step(False)
     barrier()
+    last_hits = {} if args.dump_outputs and rank == 0 else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for s in range(args.steps):
+        step(True, last_hits if s == args.steps - 1 else None)
     barrier()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if last_hits is not None:
+        dump_outputs(args.dump_outputs, [("hits_csv%02d" % c, hit_columns(h)) for c, h in sorted(last_hits.items())])
     for c, (kc, km) in kept.items():
         last[c] = (n_keys_of[c], kc.cpu().numpy().copy(), km.cpu().numpy().copy())
     value = n * n_csv * args.steps / elapsed

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for kib in ${KIBS:-1536 2048 2560 3072}; do
   export GF_BLOOM_KIB=$kib
-  python3 $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-parity --no-h2d "$@" > $OUT/bench_$kib.json 2> $OUT/bench_$kib.err || { echo "bench $kib failed"; tail -3 $OUT/bench_$kib.err; exit 1; }
+  python3 $REPO/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-parity --no-h2d "$@" > $OUT/bench_$kib.json 2> $OUT/bench_$kib.err || { echo "bench $kib failed"; tail -3 $OUT/bench_$kib.err; exit 1; }
   rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_$kib -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-h2d "$@" > $OUT/pmc_$kib.log 2>&1 || { echo "pmc $kib failed"; tail -3 $OUT/pmc_$kib.log; }
   python3 - $OUT $kib <<'PY'
 import csv, glob, json, sys

@@ -20,7 +20,7 @@ else
   for v in full $VARIANTS; do
     name=${v%%:*}
     lib=$REPO/genefuserust_amd/libgfmatch_$name.so; [ $name = full ] && lib=$REPO/genefuserust_amd/libgfmatch.so
-    GFMATCH_LIB=$lib python3 $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-parity --no-h2d --no-pack-sweep --no-stress "${@:2}" 2>/dev/null | \
+    GFMATCH_LIB=$lib python3 $REPO/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-parity --no-h2d --no-pack-sweep --no-stress "${@:2}" 2>/dev/null | \
       python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name', d['roofline']['kernel_ms_avg'], d['roofline']['stage_ms'])"
   done
 fi

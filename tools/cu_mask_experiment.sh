@@ -7,6 +7,6 @@
 H5=$(printf '5%.0s' $(seq 64)); H0F=$(printf '0F%.0s' $(seq 32)); HX=$(printf '00000000FFFFFFFF%.0s' $(seq 4))
 for m in full 0x$H5 0x$H0F 0x$HX; do
   if [ $m = full ]; then unset ROC_GLOBAL_CU_MASK; else export ROC_GLOBAL_CU_MASK=$m; fi
-  python3 bench.py --no-cpu-baseline --no-h2d --no-parity --steps 5 "$@" 2>/dev/null | python3 -c "
+  python3 bench.py --full --no-cpu-baseline --no-h2d --no-parity --steps 5 "$@" 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('mask', '$m'[:20], round(d['value']/1e9,3), 'G reads/s', d['roofline']['stage_ms'])"
 done

@@ -2,7 +2,7 @@
 # The stress rows at the headline's size (GPU box): profiles/<tag>_stress_*.json = bench lines of configs[1]'s workload on
 # harder gene sets / read mixes.  bash tools/stress_rows.sh <tag>
 TAG=${1:-r04}
-COMMON="--steps 10 --warmup 2 --no-cpu-baseline --no-h2d --no-pack-sweep --no-stress"
+COMMON="--steps 10 --warmup 2 --full --no-cpu-baseline --no-h2d --no-pack-sweep --no-stress"
 python bench.py $COMMON --repeat-frac 0.1 > gpurun_out/${TAG}_stress_repeat10.json 2>/dev/null
 python bench.py $COMMON --repeat-frac 0.3 > gpurun_out/${TAG}_stress_repeat30.json 2>/dev/null
 python bench.py $COMMON --low-complexity 0.05 > gpurun_out/${TAG}_stress_lowcomplexity5.json 2>/dev/null

@@ -3,7 +3,7 @@
 #   bash tools/trace_kernels.sh [bench args]
 REPO=$(pwd); OUT=$REPO/gpurun_out/trace_tmp
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o t -- python3 $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-parity "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o t -- python3 $REPO/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-parity "$@" > /dev/null 2>&1
 cd $REPO
 python3 - <<PY
 import csv
