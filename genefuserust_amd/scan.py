@@ -80,9 +80,17 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
 
 
 def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
-                          deletion_threshold: int = 50, _keep: dict = None) -> Tuple[List[ReadMatch], dict]:
+                          deletion_threshold: int = 50, _keep: dict = None,
+                          route: str = "device") -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
-    every read is mapped, then its reverse complement when it was mapable without a match."""
+    every read is mapped, then its reverse complement when it was mapable without a match.
+
+    ``route="device"``: the records stay in HBM from the FASTQ cut to the hit list — one ``gf_se_scan_device`` call
+    (single_end.py), the tail by ``finish_pair_hits``; the counters add ``retried_reads``.  ``route="host"``: the
+    records go to the host and through ``FusionMapper.scan_single_end`` (two mapping calls over host buffers, the tail
+    per matched read).  Both give the same matches and counters."""
+    if route not in ("device", "host"):
+        raise ValueError("route must be 'device' or 'host', not %r" % (route,))
     ref = FastaReader(ref_file, True)
     ref.read_all()
     fusions = Fusion.parse_csv(fusion_csv)
@@ -90,6 +98,14 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     ix.make_index()
     try:
         b, text = FastqReader(read1_file).read_all_device(ix)
+        if route == "device":
+            found, extra = _single_end_device(ix, b, text)
+            mapper = FusionMapper(ix)
+            kept, removed = mapper.filter_matches(found, deletion_threshold)
+            counters = {"reads": b.n_records, "matches_before_filtering": len(found), **removed, **extra}
+            if _keep is not None:
+                _keep.update(fusions=fusions, fusion_seq=list(ix.m_fusion_seq))
+            return FusionMapper.sort_matches(kept), counters
         off = b.offsets.cpu().numpy()
         bases, quals = b.bases.cpu().numpy().tobytes(), b.quals.cpu().numpy().tobytes()
         reads = [bases[off[i]:off[i + 1]] for i in range(b.n_records)]
@@ -112,12 +128,34 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
         ix.close()
 
 
+def _single_end_device(ix: Indexer, b, text: bytes) -> Tuple[List[ReadMatch], dict]:
+    """The matches of a FASTQ batch in HBM, in read order, through one device call (and once more with room for
+    everything when the first one overflowed)."""
+    from .single_end import scan_single_device
+    mapper = FusionMapper(ix)
+    n = b.n_records
+    max_len = max(b.max_read_len(), 1)
+    caps = dict(hits_cap=max(1024, n // 8), bytes_cap=max(1024, n // 8) * max_len)
+    rec, hb, hq, tot = scan_single_device(ix, b.bases, b.quals, b.offsets, max_len, **caps).download()
+    if tot["overflow"]:   # unusually many matches or retries: once more with room for everything
+        caps = dict(hits_cap=max(n, 1), bytes_cap=int(b.bases.numel()) + 64, retry_cap=max(n, 1))
+        rec, hb, hq, tot = scan_single_device(ix, b.bases, b.quals, b.offsets, max_len, **caps).download()
+    assert not tot["overflow"], tot
+    found: List[ReadMatch] = []
+    for i, m in finish_pair_hits(mapper, rec, hb, hq):
+        m.m_name = record_lines(b, text, i)[0]
+        found.append(m)
+    return found, {"retried_reads": tot["retried_reads"]}
+
+
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
-                           settings: Settings = None) -> Tuple[List[FusionResult], dict]:
-    """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions."""
+                           settings: Settings = None, route: str = "device") -> Tuple[List[FusionResult], dict]:
+    """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``: see
+    ``scan_single_end_files``."""
     settings = settings or Settings()
     keep: dict = {}
-    kept, counters = scan_single_end_files(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold, keep)
+    kept, counters = scan_single_end_files(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold, keep,
+                                           route=route)
     results = cluster_matches(group_and_sort(kept, len(keep["fusions"])), keep["fusions"], keep["fusion_seq"], settings)
     counters["fusions"] = len(results)
     return results, counters

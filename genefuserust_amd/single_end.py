@@ -1,0 +1,117 @@
+"""``SingleEndScanner::scan_single_end`` (src/core/sescanner.rs:183-205) for a batch of reads resident in HBM, one
+asynchronous call: ``gf_se_scan_device`` of libgfse.so (include/gf_single_end.h).
+
+libgfse.so is a library of its own on top of libgfmatch.so's public C ABI (genefuserust_amd/se_csrc/); it is loaded
+after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this tree.  The result is a ``PairScan`` in the
+format of ``gf_scan_pairs_device`` (source 1 = "r1"), so ``PairScan.download``, ``finish_pair_hits`` and
+``finish_pair_hits_device`` take it unchanged.  No CPU fallback: without the libraries and a GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional
+
+from . import _lib
+from ._lib import GF_ERR_NO_DEVICE, GF_ERR_READ_TOO_LONG, GfError
+from .indexer import Indexer
+from .read_pair import PairScan
+
+SE_LIB_PATH = os.path.join(_lib._HERE, "libgfse.so")
+
+_se = None
+
+
+def lib() -> C.CDLL:
+    """Load libgfse.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
+    libgfmatch.so than the one libgfse.so links against (two builds of the mapping in one process)."""
+    global _se
+    if _se is not None:
+        return _se
+    _lib.lib()
+    own = os.path.join(_lib._HERE, "libgfmatch.so")
+    if os.path.realpath(_lib.LIB_PATH) != os.path.realpath(own):
+        raise ImportError("GFMATCH_LIB=%s: libgfse.so links against %s; the single-end scan does not mix two builds"
+                          % (_lib.LIB_PATH, own))
+    if not os.path.exists(SE_LIB_PATH):
+        raise ImportError(
+            "libgfse.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). The single-end scan has no CPU fallback." % SE_LIB_PATH)
+    L = C.CDLL(SE_LIB_PATH)
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.gf_se_retry_capacity.argtypes = [i64]
+    L.gf_se_retry_capacity.restype = i64
+    L.gf_se_workspace_bytes.argtypes = [i64, i32, i64]
+    L.gf_se_workspace_bytes.restype = i64
+    L.gf_se_scan_device.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, i32, i64, i64, vp, i64, vp, i64, vp, vp, i64, vp,
+                                    vp]
+    L.gf_se_scan_device.restype = C.c_int
+    L.gf_se_last_error.argtypes = []
+    L.gf_se_last_error.restype = C.c_char_p
+    _se = L
+    return L
+
+
+def check(rc: int) -> int:
+    if rc < 0:
+        raise GfError(rc, lib().gf_se_last_error().decode("utf-8", "replace"))
+    return rc
+
+
+def _gene_reversed(indexer: Indexer, dev):
+    """Fusion::is_reversed() per gene as a device tensor, uploaded once per index and device."""
+    import torch
+    from .fusion_mapper import FusionMapper
+    cached = getattr(indexer, "_se_gene_rev", None)
+    if cached is None or cached.device != dev:
+        rev = FusionMapper(indexer)._rev   # (uint8, at least one element)
+        cached = torch.from_numpy(rev.copy()).to(dev)
+        indexer._se_gene_rev = cached
+    return cached
+
+
+def scan_single_device(indexer: Indexer, bases, quals, offsets, max_read_len: int, read_id_base: int = 0,
+                       hits_cap: Optional[int] = None, bytes_cap: Optional[int] = None, retry_cap: int = 0,
+                       stream=None, check_lengths: bool = True) -> PairScan:
+    """The single-end policy for the ``n = offsets.numel() - 1`` reads of ``bases`` / ``quals`` (uint8, the layout
+    ``fastq_cut_device`` writes) and ``offsets`` (int64[n+1]), all on the index's device: map every read; a read with
+    two segments in the wrong direction is searched again as its reverse complement.  One ``gf_pair_hit`` per hit
+    (``pair_id = read_id_base + r``, ``source`` 1, ``flags`` 3 on the reverse complement), in read order.
+
+    ``check_lengths``: wait for the totals and raise ``GfError(GF_ERR_READ_TOO_LONG)`` when a read is longer than
+    ``max_read_len`` (totals[5]); False leaves the call fully asynchronous and the check to the caller."""
+    import torch
+    for t in (bases, quals, offsets):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GfError(GF_ERR_NO_DEVICE, "scan_single_device takes device tensors (there is no CPU fallback)")
+    assert bases.dtype == torch.uint8 and quals.dtype == torch.uint8 and offsets.dtype == torch.int64
+    assert quals.numel() >= bases.numel() and offsets.is_contiguous() and bases.is_contiguous() and quals.is_contiguous()
+    L = lib()
+    n = offsets.numel() - 1
+    dev = bases.device
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    hits_cap = max(1024, n // 16) if hits_cap is None else int(hits_cap)
+    bytes_cap = hits_cap * max(int(max_read_len), 1) if bytes_cap is None else int(bytes_cap)
+    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
+    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    ws_bytes = int(L.gf_se_workspace_bytes(n, int(max_read_len), int(retry_cap)))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    rev = _gene_reversed(indexer, dev)
+    n_genes = len(indexer.m_fusions)
+    check(L.gf_se_scan_device(indexer._handle(), bases.data_ptr(), quals.data_ptr(), offsets.data_ptr(), bases.numel(),
+                              n, int(max_read_len), rev.data_ptr(), n_genes, int(read_id_base), int(retry_cap),
+                              ws.data_ptr(), ws_bytes, hits.data_ptr(), hits_cap, hb.data_ptr(), hq.data_ptr(), bytes_cap,
+                              totals.data_ptr(), st))
+    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
+    if stream is not None:
+        ext = torch.cuda.ExternalStream(stream, device=dev)
+        ws.record_stream(ext)
+        if check_lengths:
+            ext.synchronize()
+    if check_lengths:
+        too_long = int(totals[5].item())
+        if too_long:
+            raise GfError(GF_ERR_READ_TOO_LONG, "%d reads are longer than max_read_len = %d" % (too_long, max_read_len))
+    return PairScan(hits, hb, hq, totals)
