@@ -13,5 +13,7 @@ from .fusion_result import (FusionResult, Settings, cluster_matches, group_and_s
                             report_text)
 from .matcher import Matcher, MatcherPanic, remove_alignables  # noqa: F401
 from .fastq import FastqBatch, FastqReader, FastqReaderPair, fastq_cut_device, record_lines  # noqa: F401
+from .multi_csv_scan import (PreparedPairs, prepare_pairs_device, read_csv_list, report_names,  # noqa: F401
+                             scan_multi_csv_report, scan_prepared_pairs_device, scan_report)
 
 __version__ = "0.1.0"

@@ -1,0 +1,303 @@
+"""Multi-CSV mode from files (``FusionScan::scan_per_fusion_csv``, src/core/fusion_scan.rs:62-188): the reference and
+the FASTQ records are read once, every fusion CSV of a list file is scanned against them, and each gets its report.
+
+The paired-end scan is cut where the CSV starts to matter (libgfmcsv.so, include/gf_multi_csv.h):
+``prepare_pairs_device`` merges the pairs, gathers the reads a scan will map and packs them — once — and
+``scan_prepared_pairs_device`` maps, classifies, retries and compacts them per index, into exactly the ``PairScan``
+that ``read_pair.scan_pairs_device`` gives, so ``PairScan.download``, ``finish_pair_hits`` and
+``finish_pair_hits_device`` take it unchanged.  libgfmcsv.so is a library of its own on top of libgfmatch.so's public
+C ABI (genefuserust_amd/mc_csrc/); it is loaded after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this
+tree.  No CPU fallback: without the libraries and a GPU every compute call raises.
+
+``multi_csv.py`` (the bare mapping of resident reads over ranks) stays as it is; running this file-level scan on
+several ranks is not done here (``plan_multi_csv`` says which rank would own which CSV).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import List, NamedTuple, Optional, Sequence, Tuple
+
+from . import _lib
+from ._lib import GF_ERR_NO_DEVICE, GfError
+from .fusion_result import FusionResult, Settings, cluster_matches, group_and_sort, report_json
+from .indexer import Indexer
+from .read_pair import PairScan
+
+MC_LIB_PATH = os.path.join(_lib._HERE, "libgfmcsv.so")
+
+_mc = None
+
+
+def lib() -> C.CDLL:
+    """Load libgfmcsv.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
+    libgfmatch.so than the one libgfmcsv.so links against (two builds of the mapping in one process)."""
+    global _mc
+    if _mc is not None:
+        return _mc
+    _lib.lib()
+    own = os.path.join(_lib._HERE, "libgfmatch.so")
+    if os.path.realpath(_lib.LIB_PATH) != os.path.realpath(own):
+        raise ImportError("GFMATCH_LIB=%s: libgfmcsv.so links against %s; the multi-CSV scan does not mix two builds"
+                          % (_lib.LIB_PATH, own))
+    if not os.path.exists(MC_LIB_PATH):
+        raise ImportError(
+            "libgfmcsv.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). The multi-CSV scan has no CPU fallback." % MC_LIB_PATH)
+    L = C.CDLL(MC_LIB_PATH)
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.gf_mc_prepared_bytes.argtypes = [i64, i64, i64, i32]
+    L.gf_mc_prepared_bytes.restype = i64
+    L.gf_mc_retry_capacity.argtypes = [i64]
+    L.gf_mc_retry_capacity.restype = i64
+    L.gf_mc_scan_workspace_bytes.argtypes = [i64, i32, i64]
+    L.gf_mc_scan_workspace_bytes.restype = i64
+    L.gf_mc_pairs_prepare_device.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, vp]
+    L.gf_mc_pairs_prepare_device.restype = C.c_int
+    L.gf_mc_pairs_scan_device.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, vp, i32, i64, i64, vp, i64,
+                                          vp, i64, vp, vp, i64, vp, vp]
+    L.gf_mc_pairs_scan_device.restype = C.c_int
+    L.gf_mc_last_error.argtypes = []
+    L.gf_mc_last_error.restype = C.c_char_p
+    _mc = L
+    return L
+
+
+def check(rc: int) -> int:
+    if rc < 0:
+        raise GfError(rc, lib().gf_mc_last_error().decode("utf-8", "replace"))
+    return rc
+
+
+class PreparedPairs(NamedTuple):
+    """The CSV-independent half of a pair scan, device resident: ``buffer`` is what gf_mc_pairs_prepare_device filled
+    (merged lengths and diffs, the read lists and their packed form); the R1 / R2 tensors it was made from travel with
+    it, because the scan reads the matched reads' bases and qualities from them."""
+    buffer: "object"
+    l_bases: "object"
+    l_quals: "object"
+    l_off: "object"
+    r_bases: "object"
+    r_quals: "object"
+    r_off: "object"
+    n: int
+    max_read_len: int
+
+    def merged_pairs(self) -> int:
+        """Synchronises.  The number of pairs that merged."""
+        import torch
+        if self.n == 0:
+            return 0
+        pad = (-self.buffer.data_ptr()) % 256   # (the library aligns the caller's base to 256 bytes)
+        return int(self.buffer[pad:pad + 32].view(torch.int64)[2].item())
+
+
+def prepare_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_quals, r_off, max_read_len: int,
+                         stream=None) -> PreparedPairs:
+    """``fast_merge`` of every pair, the reads a scan maps gathered into two contiguous lists (R1 / R2 of the pairs that
+    did not merge; the merged reads) and those lists packed — everything of ``PairEndScanner::scan_pair_end`` that
+    does not depend on the fusion CSV, once, asynchronously.  ``indexer`` only names the device: the result stays valid
+    after it is closed.  Tensors as for ``read_pair.scan_pairs_device``."""
+    import torch
+    for t in (l_bases, l_quals, l_off, r_bases, r_quals, r_off):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GfError(GF_ERR_NO_DEVICE, "prepare_pairs_device takes device tensors (there is no CPU fallback)")
+    for t in (l_bases, l_quals, r_bases, r_quals):
+        assert t.dtype == torch.uint8 and t.is_contiguous()
+    n = l_off.numel() - 1
+    assert l_off.dtype == torch.int64 and r_off.dtype == torch.int64 and r_off.numel() == n + 1
+    assert l_off.is_contiguous() and r_off.is_contiguous()
+    assert l_quals.numel() >= l_bases.numel() and r_quals.numel() >= r_bases.numel()
+    L = lib()
+    dev = l_bases.device
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    nbytes = int(L.gf_mc_prepared_bytes(n, l_bases.numel(), r_bases.numel(), int(max_read_len)))
+    buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.gf_mc_pairs_prepare_device(indexer._handle(), l_bases.data_ptr(), l_quals.data_ptr(), l_off.data_ptr(),
+                                       l_bases.numel(), r_bases.data_ptr(), r_quals.data_ptr(), r_off.data_ptr(),
+                                       r_bases.numel(), n, int(max_read_len), buf.data_ptr(), nbytes, st))
+    if stream is not None:
+        buf.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return PreparedPairs(buf, l_bases, l_quals, l_off, r_bases, r_quals, r_off, n, int(max_read_len))
+
+
+def scan_prepared_pairs_device(indexer: Indexer, prepared: PreparedPairs, pair_id_base: int = 0,
+                               hits_cap: Optional[int] = None, bytes_cap: Optional[int] = None, retry_cap: int = 0,
+                               stream=None) -> PairScan:
+    """The CSV-dependent half over a ``PreparedPairs``: both read lists mapped from the packed form, the direction
+    gate, the reverse-complement retries and the ordered compaction, one asynchronous call (gf_mc_pairs_scan_device).
+    The result equals ``read_pair.scan_pairs_device`` on the same pairs, byte for byte.  ``retry_cap`` 0: the
+    library's default (n / 32: every slot is mapped); totals' overflow bit 1 says when it was too small."""
+    import torch
+    from .single_end import _gene_reversed
+    L = lib()
+    p = prepared
+    n, max_len = p.n, p.max_read_len
+    dev = p.buffer.device
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    hits_cap = max(1024, n // 16) if hits_cap is None else int(hits_cap)
+    bytes_cap = hits_cap * 2 * max(max_len, 1) if bytes_cap is None else int(bytes_cap)
+    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
+    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    ws_bytes = int(L.gf_mc_scan_workspace_bytes(n, max_len, int(retry_cap)))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    rev = _gene_reversed(indexer, dev)
+    n_genes = len(indexer.m_fusions)
+    check(L.gf_mc_pairs_scan_device(indexer._handle(), p.buffer.data_ptr(), p.l_bases.data_ptr(), p.l_quals.data_ptr(),
+                                    p.l_off.data_ptr(), p.l_bases.numel(), p.r_bases.data_ptr(), p.r_quals.data_ptr(),
+                                    p.r_off.data_ptr(), p.r_bases.numel(), n, max_len, rev.data_ptr(), n_genes,
+                                    int(pair_id_base), int(retry_cap), ws.data_ptr(), ws_bytes, hits.data_ptr(), hits_cap,
+                                    hb.data_ptr(), hq.data_ptr(), bytes_cap, totals.data_ptr(), st))
+    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
+    if stream is not None:
+        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return PairScan(hits, hb, hq, totals)
+
+
+# ---- the list file and the report names -------------------------------------------------------------------------
+
+def read_csv_list(path: str) -> List[str]:
+    """``get_fusion_csv_vec_from_input`` (fusion_scan.rs:253-280): the fusion CSVs a list file names, one per line —
+    lines trimmed, empty ones skipped, order and duplicates kept.  A named file that does not exist raises
+    ``FileNotFoundError`` (the reference prints "Fusion csv file '..' was not found." and exits); a line of more than
+    1000 bytes raises ``ValueError`` (the reference's LimitedBufReader panics)."""
+    out: List[str] = []
+    with open(path, "rb") as f:
+        for raw in f:
+            if len(raw.rstrip(b"\n")) > 1000:
+                raise ValueError("%s: a line of more than 1000 bytes" % path)
+            s = raw.decode("utf-8").strip()
+            if not s:
+                continue
+            if not os.path.isfile(s):
+                raise FileNotFoundError("Fusion csv file '%s' was not found." % s)
+            out.append(s)
+    return out
+
+
+def _rust_stem_ext(path: str) -> Tuple[str, str, Optional[str]]:
+    """(parent, file_stem, extension) as std::path::Path gives them: the extension is what follows the LAST dot of
+    the file name, and a name that only starts with a dot has none."""
+    parent, name = os.path.split(path)
+    dot = name.rfind(".")
+    if dot <= 0:
+        return parent, name, None
+    return parent, name[:dot], name[dot + 1:]
+
+
+def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
+    """``get_report_names_from_fusion_csvs`` (fusion_scan.rs:190-251) for one report file: per CSV
+    ``<parent>/<stem>_<csvstem>.<ext>``; ``[]`` for an empty ``report_file``.  A report file without an extension raises
+    ``ValueError`` (the reference unwraps it)."""
+    if not report_file:
+        return []
+    parent, stem, ext = _rust_stem_ext(report_file)
+    if ext is None:
+        raise ValueError("report file %r has no extension" % report_file)
+    return [os.path.join(parent, "%s_%s.%s" % (stem, _rust_stem_ext(c)[1], ext)) for c in csv_paths]
+
+
+# ---- the scan from files ------------------------------------------------------------------------------------------
+
+def _pairs_one_csv(ix: Indexer, prepared: PreparedPairs, l, ltext, r, rtext, deletion_threshold: int):
+    """What scan.scan_pair_end_files does after its FASTQ cut, on the prepared pairs."""
+    from .fastq import record_lines
+    from .fusion_mapper import FusionMapper
+    from .read_pair import finish_pair_hits
+    mapper = FusionMapper(ix)
+    n, max_len = prepared.n, prepared.max_read_len
+    caps = dict(hits_cap=max(1024, n // 8), bytes_cap=max(1024, n // 8) * 2 * max_len)
+    rec, hb, hq, tot = scan_prepared_pairs_device(ix, prepared, **caps).download()
+    if tot["overflow"]:   # unusually many matches or retries: once more with room for everything
+        caps = dict(hits_cap=3 * n, bytes_cap=2 * int(l.bases.numel() + r.bases.numel()) + 64, retry_cap=3 * n)
+        rec, hb, hq, tot = scan_prepared_pairs_device(ix, prepared, **caps).download()
+    found = []
+    for i, m in finish_pair_hits(mapper, rec, hb, hq):
+        # a match on R2 (or its reverse complement) carries R2's name; anything else R1's
+        m.m_name = record_lines(r, rtext, i)[0] if m.m_source == "r2" else record_lines(l, ltext, i)[0]
+        if m.m_source == "merged":
+            m.m_name += b" merged_diff_%d" % m.m_merge_diff
+        found.append(m)
+    kept, removed = mapper.filter_matches(found, deletion_threshold)
+    counters = {"pairs": n, "matches_before_filtering": len(found), "merged_pairs": tot["merged_pairs"],
+                "retried_reads": tot["retried_reads"], **removed}
+    return FusionMapper.sort_matches(kept), counters
+
+
+def _single_one_csv(ix: Indexer, b, text, deletion_threshold: int):
+    """What scan.scan_single_end_files(route="device") does after its FASTQ cut."""
+    from .fusion_mapper import FusionMapper
+    from .scan import _single_end_device
+    found, extra = _single_end_device(ix, b, text)
+    kept, removed = FusionMapper(ix).filter_matches(found, deletion_threshold)
+    counters = {"reads": b.n_records, "matches_before_filtering": len(found), **removed, **extra}
+    return FusionMapper.sort_matches(kept), counters
+
+
+def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
+                          settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
+                          time: str = "") -> List[Tuple[str, List[FusionResult], dict]]:
+    """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
+    ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
+    alone.  The FASTA is read once and the FASTQ cut once; with ``read2_file`` the pairs are prepared once.  Per CSV:
+    parse it, build its index, scan, finish, filter, sort, cluster; the index is closed before the next one.  With
+    ``json_file`` each entry's ``report_json`` goes to its ``report_names`` name — two entries with the same stem share
+    a name and the later one overwrites the earlier, as in the reference."""
+    from .fastq import FastqReader, FastqReaderPair
+    from .indexer import FastaReader, Fusion
+    settings = settings or Settings()
+    csvs = read_csv_list(csv_list_file)
+    names = report_names(json_file, csvs)
+    ref = FastaReader(ref_file, True)
+    ref.read_all()
+    out: List[Tuple[str, List[FusionResult], dict]] = []
+    reads = prepared = None
+    for k, csv in enumerate(csvs):
+        fusions = Fusion.parse_csv(csv)
+        ix = Indexer(ref.m_all_contigs, fusions, device)
+        ix.make_index()
+        try:
+            if reads is None:   # (the first index names the device the records go to)
+                if read2_file:
+                    reads = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
+                    (l, _), (r, _) = reads
+                    prepared = prepare_pairs_device(ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets,
+                                                    max(l.max_read_len(), r.max_read_len(), 1))
+                else:
+                    reads = FastqReader(read1_file).read_all_device(ix)
+            if read2_file:
+                (l, ltext), (r, rtext) = reads
+                kept, counters = _pairs_one_csv(ix, prepared, l, ltext, r, rtext, settings.deletion_threshold)
+            else:
+                kept, counters = _single_one_csv(ix, reads[0], reads[1], settings.deletion_threshold)
+            results = cluster_matches(group_and_sort(kept, len(fusions)), fusions, list(ix.m_fusion_seq), settings)
+            counters["fusions"] = len(results)
+        finally:
+            ix.close()
+        if names:
+            with open(names[k], "w") as f:
+                f.write(report_json(results, command, version, time, settings))
+        out.append((csv, results, counters))
+    return out
+
+
+def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
+                settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = ""):
+    """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
+    to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
+    ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
+    gives ``scan_multi_csv_report``'s list."""
+    from . import scan
+    if _rust_stem_ext(fusion_file)[2] == "csv":
+        if read2_file:
+            results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings)
+        else:
+            results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings)
+        if json_file:
+            with open(json_file, "w") as f:
+                f.write(report_json(results, command, version, time, settings))
+        return results, counters
+    return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
+                                 version, time)
