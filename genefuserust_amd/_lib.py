@@ -231,3 +231,20 @@ def check(rc: int) -> int:
     if rc < 0:
         raise GfError(rc, lib().gf_last_error().decode("utf-8", "replace"))
     return rc
+
+
+def load_companion(path: str, feature: str) -> C.CDLL:
+    """Load a library that is built on libgfmatch.so's public C ABI and lies next to it (genefuserust_amd/scan_csrc/),
+    after libgfmatch.so, so that both refer to the one libgfmatch.so of this tree.  Raises if it has not been built, or
+    if GFMATCH_LIB names another libgfmatch.so than the one it links against (two builds of the mapping in one
+    process).  ``feature`` names what the library does, for the messages."""
+    lib()
+    name, own = os.path.basename(path), os.path.join(_HERE, "libgfmatch.so")
+    if os.path.realpath(LIB_PATH) != os.path.realpath(own):
+        raise ImportError("GFMATCH_LIB=%s: %s links against %s; the %s does not mix two builds"
+                          % (LIB_PATH, name, own, feature))
+    if not os.path.exists(path):
+        raise ImportError(
+            "%s not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). The %s has no CPU fallback." % (name, path, feature))
+    return C.CDLL(path)

@@ -6,7 +6,7 @@ The paired-end scan is cut where the CSV starts to matter (libgfmcsv.so, include
 ``scan_prepared_pairs_device`` maps, classifies, retries and compacts them per index, into exactly the ``PairScan``
 that ``read_pair.scan_pairs_device`` gives, so ``PairScan.download``, ``finish_pair_hits`` and
 ``finish_pair_hits_device`` take it unchanged.  libgfmcsv.so is a library of its own on top of libgfmatch.so's public
-C ABI (genefuserust_amd/mc_csrc/); it is loaded after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this
+C ABI (genefuserust_amd/scan_csrc/); it is loaded after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this
 tree.  No CPU fallback: without the libraries and a GPU every compute call raises.
 
 ``multi_csv.py`` (the bare mapping of resident reads over ranks) stays as it is; running this file-level scan on
@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import GF_ERR_NO_DEVICE, GfError
 from .fusion_result import FusionResult, Settings, cluster_matches, group_and_sort, report_json
 from .indexer import Indexer
-from .read_pair import PairScan
+from .read_pair import PairScan, companion_scan, gene_reversed_device
 
 MC_LIB_PATH = os.path.join(_lib._HERE, "libgfmcsv.so")
 
@@ -35,16 +35,7 @@ def lib() -> C.CDLL:
     global _mc
     if _mc is not None:
         return _mc
-    _lib.lib()
-    own = os.path.join(_lib._HERE, "libgfmatch.so")
-    if os.path.realpath(_lib.LIB_PATH) != os.path.realpath(own):
-        raise ImportError("GFMATCH_LIB=%s: libgfmcsv.so links against %s; the multi-CSV scan does not mix two builds"
-                          % (_lib.LIB_PATH, own))
-    if not os.path.exists(MC_LIB_PATH):
-        raise ImportError(
-            "libgfmcsv.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The multi-CSV scan has no CPU fallback." % MC_LIB_PATH)
-    L = C.CDLL(MC_LIB_PATH)
+    L = _lib.load_companion(MC_LIB_PATH, "multi-CSV scan")
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.gf_mc_prepared_bytes.argtypes = [i64, i64, i64, i32]
     L.gf_mc_prepared_bytes.restype = i64
@@ -128,32 +119,18 @@ def scan_prepared_pairs_device(indexer: Indexer, prepared: PreparedPairs, pair_i
     gate, the reverse-complement retries and the ordered compaction, one asynchronous call (gf_mc_pairs_scan_device).
     The result equals ``read_pair.scan_pairs_device`` on the same pairs, byte for byte.  ``retry_cap`` 0: the
     library's default (n / 32: every slot is mapped); totals' overflow bit 1 says when it was too small."""
-    import torch
-    from .single_end import _gene_reversed
     L = lib()
     p = prepared
     n, max_len = p.n, p.max_read_len
     dev = p.buffer.device
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     hits_cap = max(1024, n // 16) if hits_cap is None else int(hits_cap)
     bytes_cap = hits_cap * 2 * max(max_len, 1) if bytes_cap is None else int(bytes_cap)
-    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
-    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    totals = torch.zeros(8, dtype=torch.int64, device=dev)
     ws_bytes = int(L.gf_mc_scan_workspace_bytes(n, max_len, int(retry_cap)))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    rev = _gene_reversed(indexer, dev)
-    n_genes = len(indexer.m_fusions)
-    check(L.gf_mc_pairs_scan_device(indexer._handle(), p.buffer.data_ptr(), p.l_bases.data_ptr(), p.l_quals.data_ptr(),
-                                    p.l_off.data_ptr(), p.l_bases.numel(), p.r_bases.data_ptr(), p.r_quals.data_ptr(),
-                                    p.r_off.data_ptr(), p.r_bases.numel(), n, max_len, rev.data_ptr(), n_genes,
-                                    int(pair_id_base), int(retry_cap), ws.data_ptr(), ws_bytes, hits.data_ptr(), hits_cap,
-                                    hb.data_ptr(), hq.data_ptr(), bytes_cap, totals.data_ptr(), st))
-    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
-    if stream is not None:
-        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
-    return PairScan(hits, hb, hq, totals)
+    head = (indexer._handle(), p.buffer.data_ptr(), p.l_bases.data_ptr(), p.l_quals.data_ptr(), p.l_off.data_ptr(),
+            p.l_bases.numel(), p.r_bases.data_ptr(), p.r_quals.data_ptr(), p.r_off.data_ptr(), p.r_bases.numel(), n,
+            max_len, gene_reversed_device(indexer, dev).data_ptr(), len(indexer.m_fusions), int(pair_id_base),
+            int(retry_cap))
+    return companion_scan(check, L.gf_mc_pairs_scan_device, head, dev, ws_bytes, hits_cap, bytes_cap, stream)
 
 
 # ---- the list file and the report names -------------------------------------------------------------------------

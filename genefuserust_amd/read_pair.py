@@ -122,6 +122,37 @@ class PairScan(NamedTuple):
         return rec, self.bases[:nb].cpu().numpy().tobytes(), self.quals[:nb].cpu().numpy().tobytes(), tot
 
 
+def gene_reversed_device(indexer: Indexer, dev):
+    """Fusion::is_reversed() per gene as a device tensor, uploaded once per index and device."""
+    import torch
+    cached = getattr(indexer, "_gene_rev_device", None)
+    if cached is None or cached.device != dev:
+        rev = FusionMapper(indexer)._rev   # (uint8, at least one element)
+        cached = torch.from_numpy(rev.copy()).to(dev)
+        indexer._gene_rev_device = cached
+    return cached
+
+
+def companion_scan(check, fn, head, dev, ws_bytes: int, hits_cap: int, bytes_cap: int, stream) -> PairScan:
+    """What the scans of libgfse.so and libgfmcsv.so share around their call: the outputs of a ``PairScan`` and the
+    workspace are allocated on ``dev``, ``fn(*head, workspace, its size, hits, hits_cap, hit bases, hit quals,
+    bytes_cap, totals, stream)`` is called through ``check``, and the workspace is tied to ``stream`` (None: the
+    current one)."""
+    import torch
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
+    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    check(fn(*head, ws.data_ptr(), ws_bytes, hits.data_ptr(), hits_cap, hb.data_ptr(), hq.data_ptr(), bytes_cap,
+             totals.data_ptr(), st))
+    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
+    if stream is not None:
+        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return PairScan(hits, hb, hq, totals)
+
+
 def scan_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_quals, r_off, max_read_len: int,
                       pair_id_base: int = 0, hits_cap: Optional[int] = None, bytes_cap: Optional[int] = None,
                       retry_cap: int = 0, stream=None, l_qual_off=None, r_qual_off=None) -> PairScan:

@@ -19,93 +19,23 @@
 // that a wavefront reads and writes consecutive pairs.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/gf_multi_csv.h"
+#include "gf_scan_common.h"
 
-#define GF_MC_THREADS 256
-#define GF_MC_TILE GF_MC_THREADS
-#define GF_MC_SCAN_THREADS 1024
+#define GF_MC_TILE GF_SCAN_THREADS
 #define GF_MC_SCAN_JOBS 4
-
-#define GF_MC_NONE 0u
-#define GF_MC_HIT 1u    // two segments in the required direction: a hit on the read as it is
-#define GF_MC_RETRY 2u  // two segments, wrong direction: its reverse complement is searched
-
-// Indexer::in_required_direction (indexer.rs:541-608) for a two-segment mapping.  Restated from
-// csrc/gf_pair_kernels.h (gf_dev_required_direction), which this library does not include: a second copy of that
-// header's kernels under the same names would make two kernels of one name in a profile.
-__device__ __forceinline__ bool gf_mc_required_direction(const gf_seqmatch& a, const gf_seqmatch& b,
-                                                         const uint8_t* __restrict__ rev, int n_genes) {
-  const bool swap = a.seq_start > b.seq_start;
-  const gf_seqmatch& left = swap ? b : a;
-  const gf_seqmatch& right = swap ? a : b;
-  if (left.position > 0 && right.position > 0) return true;
-  if (left.position < 0 && right.position < 0) return false;
-  const bool lrev = rev && left.contig >= 0 && left.contig < n_genes && rev[left.contig] != 0;
-  const bool rrev = rev && right.contig >= 0 && right.contig < n_genes && rev[right.contig] != 0;
-  if (lrev && !rrev) return false;
-  if (!lrev && rrev) return true;
-  if (left.contig < right.contig) return true;
-  return false;  // (the reference's same-contig test compares left with itself, :598: never true)
-}
-
-// SequenceRead::reverse_complement (read.rs:243-261 over sequence.rs:22-60): complement to UPPER case, anything but
-// ACGTacgt -> N.  Restated from csrc/gf_pair_kernels.h (gf_complement_base).
-__device__ __forceinline__ uint8_t gf_mc_complement(uint8_t c) {
-  switch (c) {
-    case 'A': case 'a': return 'T';
-    case 'T': case 't': return 'A';
-    case 'C': case 'c': return 'G';
-    case 'G': case 'g': return 'C';
-    default: return 'N';
-  }
-}
-
-// block-wide exclusive scan of two values at once (GF_MC_THREADS = 4 wavefronts): ea / eb the thread's exclusive
-// prefix, ta / tb the block's totals
-__device__ __forceinline__ void gf_mc_block_scan2(int a, long long b, int* s_a, long long* s_b, int& ea, long long& eb,
-                                                  int& ta, long long& tb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int xa = a;
-  long long xb = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ya = __shfl_up(xa, o);
-    const long long yb = __shfl_up(xb, o);
-    if (lane >= o) { xa += ya; xb += yb; }
-  }
-  if (lane == 63) { s_a[wave] = xa; s_b[wave] = xb; }
-  __syncthreads();
-  int ba = 0; long long bb = 0;
-  ta = 0; tb = 0;
-#pragma unroll
-  for (int w = 0; w < GF_MC_THREADS / 64; ++w) {
-    if (w < wave) { ba += s_a[w]; bb += s_b[w]; }
-    ta += s_a[w]; tb += s_b[w];
-  }
-  ea = ba + xa - a;
-  eb = bb + xb - b;
-  __syncthreads();  // (s_a / s_b are reused by the next scan of the block)
-}
 
 // ---- exclusive scan of per-tile totals: block b scans job b ----
 // Thread t takes a run of consecutive totals, the runs' sums are scanned across the block, every total's offset is
 // its run's base plus its place in the run.  10 M pairs are 39 063 tiles: 39 totals per thread.
-struct GfMcScanJob {
-  const uint32_t* tile_counts;
-  int64_t* tile_offsets;
-  int64_t* d_total;
-};
-struct GfMcScanJobs { GfMcScanJob j[GF_MC_SCAN_JOBS]; };
+struct GfMcScanJobs { GfScanJob j[GF_MC_SCAN_JOBS]; };
 
-__global__ __launch_bounds__(GF_MC_SCAN_THREADS) void gf_mc_k_scan(GfMcScanJobs jobs, int64_t ntiles) {
+__global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_mc_k_scan(GfMcScanJobs jobs, int64_t ntiles) {
   const uint32_t* __restrict__ cnt = jobs.j[blockIdx.x].tile_counts;
   int64_t* __restrict__ off = jobs.j[blockIdx.x].tile_offsets;
-  __shared__ long long s_w[GF_MC_SCAN_THREADS / 64];
+  __shared__ long long s_w[GF_SCAN_TOTALS_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t per = (ntiles + GF_MC_SCAN_THREADS - 1) / GF_MC_SCAN_THREADS;
+  const int64_t per = (ntiles + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
   const int64_t t0 = (int64_t)threadIdx.x * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
   long long mine = 0;
   for (int64_t t = t0; t < t1; ++t) mine += cnt[t];
@@ -118,7 +48,7 @@ __global__ __launch_bounds__(GF_MC_SCAN_THREADS) void gf_mc_k_scan(GfMcScanJobs 
   if (lane == 63) s_w[wave] = y;
   __syncthreads();
   long long base = 0, total = 0;
-  for (int w = 0; w < GF_MC_SCAN_THREADS / 64; ++w) {
+  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
     if (w < wave) base += s_w[w];
     total += s_w[w];
   }
@@ -134,20 +64,20 @@ __global__ __launch_bounds__(GF_MC_SCAN_THREADS) void gf_mc_k_scan(GfMcScanJobs 
 
 // What a tile's pairs put into the two lists.  tc: four uint32 arrays of ntiles — unmerged pairs, the bytes of their
 // R1 + R2, merged pairs, the bytes of their merged reads.
-__global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_tile_counts(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_mc_k_tile_counts(
     const int32_t* __restrict__ m_len, const int64_t* __restrict__ l_off, const int64_t* __restrict__ r_off, int64_t n,
     uint32_t* __restrict__ tc_uc, uint32_t* __restrict__ tc_ub, uint32_t* __restrict__ tc_mc,
     uint32_t* __restrict__ tc_mb) {
-  __shared__ int s_a[GF_MC_THREADS / 64];
-  __shared__ long long s_b[GF_MC_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t p = (int64_t)blockIdx.x * GF_MC_TILE + threadIdx.x;
   const int ml = p < n ? m_len[p] : 0;
   const bool un = p < n && ml <= 0;
   long long ub = 0;
   if (un) ub = (l_off[p + 1] - l_off[p]) + (r_off[p + 1] - r_off[p]);
   int e, tu, tm; long long eb, tub, tmb;
-  gf_mc_block_scan2(un ? 1 : 0, ub, s_a, s_b, e, eb, tu, tub);
-  gf_mc_block_scan2(ml > 0 ? 1 : 0, ml > 0 ? ml : 0, s_a, s_b, e, eb, tm, tmb);
+  gf_scan_block_scan2(un ? 1 : 0, ub, s_a, s_b, e, eb, tu, tub);
+  gf_scan_block_scan2(ml > 0 ? 1 : 0, ml > 0 ? ml : 0, s_a, s_b, e, eb, tm, tmb);
   if (threadIdx.x == 0) {
     tc_uc[blockIdx.x] = (uint32_t)tu;
     tc_ub[blockIdx.x] = (uint32_t)tub;
@@ -164,14 +94,14 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_tile_counts(
 // chunk of that range at a time, finds the read it starts in by a binary search over the tile's (at most 512) starts
 // in LDS, and where the whole chunk lies inside one read — all but two chunks per read — moves it with one 16-byte
 // load and one aligned 16-byte store; the chunks across a read boundary, and the range's ragged ends, go byte by byte.
-__global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_gather(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_mc_k_gather(
     const uint8_t* __restrict__ l_bases, const int64_t* __restrict__ l_off, const uint8_t* __restrict__ r_bases,
     const int64_t* __restrict__ r_off, const int32_t* __restrict__ m_len, int64_t n,
     const int64_t* __restrict__ to_uc, const int64_t* __restrict__ to_ub, const int64_t* __restrict__ to_mc,
     const int64_t* __restrict__ to_mb, const int64_t* __restrict__ d_ub_total, int32_t* __restrict__ rank,
     int64_t* __restrict__ u_off, int64_t* __restrict__ m_off, int64_t* __restrict__ m_pos, uint8_t* __restrict__ out) {
-  __shared__ int s_a[GF_MC_THREADS / 64];
-  __shared__ long long s_b[GF_MC_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   __shared__ uint32_t s_rel[2 * GF_MC_TILE + 1];        // start of the tile's unmerged read j within the tile's bytes
   __shared__ const uint8_t* s_src[2 * GF_MC_TILE];      // where it comes from
   const int tid = threadIdx.x;
@@ -185,8 +115,8 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_gather(
     ro = r_off[p]; len2 = (int)(r_off[p + 1] - ro);
   }
   int eu, tu, em, tm; long long ebu, tbu, ebm, tbm;
-  gf_mc_block_scan2(un ? 1 : 0, (long long)len1 + len2, s_a, s_b, eu, ebu, tu, tbu);
-  gf_mc_block_scan2(ml > 0 ? 1 : 0, ml > 0 ? ml : 0, s_a, s_b, em, ebm, tm, tbm);
+  gf_scan_block_scan2(un ? 1 : 0, (long long)len1 + len2, s_a, s_b, eu, ebu, tu, tbu);
+  gf_scan_block_scan2(ml > 0 ? 1 : 0, ml > 0 ? ml : 0, s_a, s_b, em, ebm, tm, tbm);
   const int64_t U = to_uc[blockIdx.x], UB = to_ub[blockIdx.x];
   if (un) {
     const int64_t k = U + eu;
@@ -208,7 +138,7 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_gather(
   if (tbu == 0) return;
   const int nslots = 2 * tu;
   const int64_t D0 = UB, D1 = UB + tbu;
-  for (int64_t c = (D0 >> 4) + tid; c < ((D1 + 15) >> 4); c += GF_MC_THREADS) {
+  for (int64_t c = (D0 >> 4) + tid; c < ((D1 + 15) >> 4); c += GF_SCAN_THREADS) {
     const int64_t b0 = c * 16 > D0 ? c * 16 : D0;
     const int64_t b1 = c * 16 + 16 < D1 ? c * 16 + 16 : D1;
     const uint32_t rel = (uint32_t)(b0 - D0);
@@ -277,41 +207,17 @@ __device__ __forceinline__ void gf_mc_candidate(const GfMcIn& P, int64_t p, int 
 __device__ __forceinline__ uint32_t gf_mc_status(const GfMcIn& P, int64_t p, int s, int32_t& len) {
   const uint8_t* b; const uint8_t* q; uint8_t cnt; const gf_seqmatch* m;
   gf_mc_candidate(P, p, s, b, q, len, cnt, m);
-  if (cnt != 2) return GF_MC_NONE;  // mapping.len() < 2: not mapable (fusion_mapper.rs:107-115)
-  return gf_mc_required_direction(m[0], m[1], P.rev, P.n_genes) ? GF_MC_HIT : GF_MC_RETRY;
-}
-
-// The reads that the lanes in `mask` have to write, one after the other, every read by all 64 lanes of the
-// wavefront (lane j: bytes j, j + 64, ..): hits and retries are a few per thousand pairs, and a lane that copied
-// its own read byte by byte would be alone in its wavefront with one round trip per byte.  revcomp: the read's
-// reverse complement, its qualities reversed.
-__device__ __forceinline__ void gf_mc_wave_write(uint64_t mask, const uint8_t* b, const uint8_t* q, int len,
-                                                 long long out, uint8_t* __restrict__ ob, uint8_t* __restrict__ oq,
-                                                 bool revcomp) {
-  const int lane = threadIdx.x & 63;
-  while (mask) {
-    const int l = __builtin_ctzll(mask);
-    mask &= mask - 1;
-    const uint8_t* bb = (const uint8_t*)__shfl((unsigned long long)b, l);
-    const uint8_t* qq = (const uint8_t*)__shfl((unsigned long long)q, l);
-    const int ln = __shfl(len, l);
-    const long long o = __shfl(out, l);
-#pragma unroll 1
-    for (int j = lane; j < ln; j += 64) {
-      const int src = revcomp ? ln - 1 - j : j;
-      ob[o + j] = revcomp ? gf_mc_complement(bb[src]) : bb[src];
-      oq[o + j] = qq[src];
-    }
-  }
+  if (cnt != 2) return GF_SCAN_NONE;  // mapping.len() < 2: not mapable (fusion_mapper.rs:107-115)
+  return gf_scan_required_direction(m[0], m[1], P.rev, P.n_genes) ? GF_SCAN_HIT : GF_SCAN_RETRY;
 }
 
 // ---- classify: which candidates matched as they are, which are searched again reversed ----
 // st[3p + s]; tile_rc / tile_rb: retries (reads / bytes) per tile.
-__global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_classify(GfMcIn P, int64_t n, uint8_t* __restrict__ st,
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_mc_k_classify(GfMcIn P, int64_t n, uint8_t* __restrict__ st,
                                                                   uint32_t* __restrict__ tile_rc,
                                                                   uint32_t* __restrict__ tile_rb) {
-  __shared__ int s_a[GF_MC_THREADS / 64];
-  __shared__ long long s_b[GF_MC_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t p = (int64_t)blockIdx.x * GF_MC_TILE + threadIdx.x;
   int rc = 0;
   long long rb = 0;
@@ -319,15 +225,15 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_classify(GfMcIn P, int6
     const bool is_merged = P.m_len[p] > 0;
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-      uint32_t v = GF_MC_NONE;
+      uint32_t v = GF_SCAN_NONE;
       int32_t len = 0;
       if (is_merged ? s == 0 : s != 0) v = gf_mc_status(P, p, s, len);
       st[3 * p + s] = (uint8_t)v;
-      if (v == GF_MC_RETRY) { rc += 1; rb += len; }
+      if (v == GF_SCAN_RETRY) { rc += 1; rb += len; }
     }
   }
   int ea, ta; long long eb, tb;
-  gf_mc_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
+  gf_scan_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
   if (threadIdx.x == 0) {
     tile_rc[blockIdx.x] = (uint32_t)ta;
     tile_rb[blockIdx.x] = (uint32_t)tb;
@@ -337,19 +243,19 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_classify(GfMcIn P, int6
 // ---- retry_write: the reverse complements of the retried reads, back to back, in candidate order ----
 // slot_of[3p + s] = index of the candidate in the retry batch, -1 for one beyond the capacities (gf_mc_k_retry_tail
 // then empties the whole retry pass and raises the overflow bit).
-__global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_retry_write(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_mc_k_retry_write(
     GfMcIn P, int64_t n, const uint8_t* __restrict__ st, const int64_t* __restrict__ tile_off_rc,
     const int64_t* __restrict__ tile_off_rb, int64_t cap_reads, int64_t cap_bytes, int64_t* __restrict__ r_off,
     uint8_t* __restrict__ r_bases, uint8_t* __restrict__ r_quals, int32_t* __restrict__ slot_of) {
-  __shared__ int s_a[GF_MC_THREADS / 64];
-  __shared__ long long s_b[GF_MC_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t p = (int64_t)blockIdx.x * GF_MC_TILE + threadIdx.x;
   int rc = 0;
   long long rb = 0;
   if (p < n) {
 #pragma unroll
     for (int s = 0; s < 3; ++s)
-      if (st[3 * p + s] == GF_MC_RETRY) {
+      if (st[3 * p + s] == GF_SCAN_RETRY) {
         const uint8_t* b; const uint8_t* q; int32_t len; uint8_t cnt; const gf_seqmatch* m;
         gf_mc_candidate(P, p, s, b, q, len, cnt, m);
         rc += 1;
@@ -357,13 +263,13 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_retry_write(
       }
   }
   int ea, ta; long long eb, tb;
-  gf_mc_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
+  gf_scan_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
   if (__ballot(rc != 0) == 0) return;  // (whole wavefronts: the reads are written by all 64 lanes)
   int64_t k_out = tile_off_rc[blockIdx.x] + ea;
   int64_t b_out = tile_off_rb[blockIdx.x] + eb;
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
-    const bool mine = p < n && st[3 * p + s] == GF_MC_RETRY;
+    const bool mine = p < n && st[3 * p + s] == GF_SCAN_RETRY;
     const uint8_t* b = nullptr; const uint8_t* q = nullptr; int32_t len = 0; uint8_t cnt; const gf_seqmatch* m;
     bool fits = false;
     if (mine) {
@@ -372,7 +278,7 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_retry_write(
       slot_of[3 * p + s] = fits ? (int32_t)k_out : -1;
       if (fits) r_off[k_out] = b_out;
     }
-    gf_mc_wave_write(__ballot(fits), b, q, len, (long long)b_out, r_bases, r_quals, true);
+    gf_scan_wave_write(__ballot(fits), b, q, len, (long long)b_out, r_bases, r_quals, true);
     if (mine) {
       k_out += 1;
       b_out += len;
@@ -380,21 +286,12 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_retry_write(
   }
 }
 
-// offsets of the unused retry slots (empty reads at the end of the retry bytes) and the overflow bit.  Over capacity
-// the whole retry pass is emptied (every offset 0): a partly searched batch would look like a result.
+// the unused retry slots emptied, the overflow bit (gf_scan_common.h)
 __global__ void gf_mc_k_retry_tail(const int64_t* __restrict__ d_n_retry, const int64_t* __restrict__ d_retry_bytes,
                                    int64_t cap_reads, int64_t cap_bytes, int64_t* __restrict__ r_off,
                                    int64_t* __restrict__ totals) {
-  const int64_t nr = *d_n_retry, nb = *d_retry_bytes;
-  const bool over = nr > cap_reads || nb > cap_bytes;
-  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= cap_reads; k += (int64_t)gridDim.x * blockDim.x) {
-    if (over) r_off[k] = 0;
-    else if (k >= nr) r_off[k] = nb;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    totals[3] = nr;
-    if (over) totals[4] |= 1;
-  }
+  gf_scan_retry_tail(d_n_retry, d_retry_bytes, cap_reads, cap_bytes, r_off, totals,
+                     (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // ---- final: the matches of the pairs, in the reference's push order.  WRITE = false: hits and their bytes per
@@ -412,23 +309,23 @@ struct GfMcFinalIn {
 __device__ __forceinline__ bool gf_mc_is_hit(const GfMcIn& P, const GfMcFinalIn& F, int64_t p, int s, int& rc_slot) {
   const uint8_t v = F.st[3 * p + s];
   rc_slot = -1;
-  if (v == GF_MC_HIT) return true;
-  if (v != GF_MC_RETRY) return false;
+  if (v == GF_SCAN_HIT) return true;
+  if (v != GF_SCAN_RETRY) return false;
   const int32_t k = F.slot_of[3 * p + s];
   if (k < 0 || F.cR[k] != 2) return false;
-  if (!gf_mc_required_direction(F.mR[2 * (int64_t)k], F.mR[2 * (int64_t)k + 1], P.rev, P.n_genes)) return false;
+  if (!gf_scan_required_direction(F.mR[2 * (int64_t)k], F.mR[2 * (int64_t)k + 1], P.rev, P.n_genes)) return false;
   rc_slot = k;
   return true;
 }
 
 template <bool WRITE>
-__global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_final(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_mc_k_final(
     GfMcIn P, GfMcFinalIn F, int64_t n, int64_t pair_id_base, uint32_t* __restrict__ tile_hc,
     uint32_t* __restrict__ tile_hb, const int64_t* __restrict__ tile_off_hc, const int64_t* __restrict__ tile_off_hb,
     gf_pair_hit* __restrict__ hits, int64_t hits_cap, uint8_t* __restrict__ out_bases, uint8_t* __restrict__ out_quals,
     int64_t bytes_cap) {
-  __shared__ int s_a[GF_MC_THREADS / 64];
-  __shared__ long long s_b[GF_MC_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t p = (int64_t)blockIdx.x * GF_MC_TILE + threadIdx.x;
   int hc = 0;
   long long hb = 0;
@@ -437,7 +334,7 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_final(
   if (p < n) {
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-      if (F.st[3 * p + s] == GF_MC_NONE) continue;
+      if (F.st[3 * p + s] == GF_SCAN_NONE) continue;
       if (gf_mc_is_hit(P, F, p, s, slot[s])) {
         const uint8_t* b; const uint8_t* q; int32_t len; uint8_t cnt; const gf_seqmatch* m;
         gf_mc_candidate(P, p, s, b, q, len, cnt, m);
@@ -448,7 +345,7 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_final(
     }
   }
   int ea, ta; long long eb, tb;
-  gf_mc_block_scan2(hc, hb, s_a, s_b, ea, eb, ta, tb);
+  gf_scan_block_scan2(hc, hb, s_a, s_b, ea, eb, ta, tb);
   if (!WRITE) {
     if (threadIdx.x == 0) {
       tile_hc[blockIdx.x] = (uint32_t)ta;
@@ -487,7 +384,7 @@ __global__ __launch_bounds__(GF_MC_THREADS) void gf_mc_k_final(
       }
       bytes_fit = b_out + len <= bytes_cap;
     }
-    gf_mc_wave_write(__ballot(bytes_fit), b, q, len, (long long)b_out, out_bases, out_quals, false);
+    gf_scan_wave_write(__ballot(bytes_fit), b, q, len, (long long)b_out, out_bases, out_quals, false);
     if (mine) {
       k_out += 1;
       b_out += len;

@@ -12,49 +12,11 @@
 // GF_SE_PER per thread, so that a batch of 20 M reads has 4 883 tiles and one block scans them.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/gf_single_end.h"
+#include "gf_scan_common.h"
 
-#define GF_SE_THREADS 256
 #define GF_SE_PER 16
-#define GF_SE_TILE (GF_SE_THREADS * GF_SE_PER)
-#define GF_SE_SCAN_THREADS 1024
-
-#define GF_SE_NONE 0u
-#define GF_SE_HIT 1u    // two segments in the required direction: a hit on the read as it is
-#define GF_SE_RETRY 2u  // two segments, wrong direction: its reverse complement is searched
-
-// Indexer::in_required_direction (indexer.rs:541-608) for a two-segment mapping.  Restated from
-// csrc/gf_pair_kernels.h (gf_dev_required_direction), which this library does not include: a second copy of that
-// header's kernels under the same names would make two kernels of one name in a profile.
-__device__ __forceinline__ bool gf_se_required_direction(const gf_seqmatch& a, const gf_seqmatch& b,
-                                                         const uint8_t* __restrict__ rev, int n_genes) {
-  const bool swap = a.seq_start > b.seq_start;
-  const gf_seqmatch& left = swap ? b : a;
-  const gf_seqmatch& right = swap ? a : b;
-  if (left.position > 0 && right.position > 0) return true;
-  if (left.position < 0 && right.position < 0) return false;
-  const bool lrev = rev && left.contig >= 0 && left.contig < n_genes && rev[left.contig] != 0;
-  const bool rrev = rev && right.contig >= 0 && right.contig < n_genes && rev[right.contig] != 0;
-  if (lrev && !rrev) return false;
-  if (!lrev && rrev) return true;
-  if (left.contig < right.contig) return true;
-  return false;  // (the reference's same-contig test compares left with itself, :598: never true)
-}
-
-// SequenceRead::reverse_complement (read.rs:243-261 over sequence.rs:22-60): complement to UPPER case, anything but
-// ACGTacgt -> N.  Restated from csrc/gf_pair_kernels.h (gf_complement_base).
-__device__ __forceinline__ uint8_t gf_se_complement(uint8_t c) {
-  switch (c) {
-    case 'A': case 'a': return 'T';
-    case 'T': case 't': return 'A';
-    case 'C': case 'c': return 'G';
-    case 'G': case 'g': return 'C';
-    default: return 'N';
-  }
-}
+#define GF_SE_TILE (GF_SCAN_THREADS * GF_SE_PER)
 
 // the thread's GF_SE_PER bytes of a per-read byte array: one 16-byte load where the address allows it, 0 beyond n
 __device__ __forceinline__ void gf_se_bytes16(const uint8_t* __restrict__ a, int64_t r0, int64_t n,
@@ -71,41 +33,14 @@ __device__ __forceinline__ void gf_se_bytes16(const uint8_t* __restrict__ a, int
   }
 }
 
-// block-wide exclusive scan of two values at once (GF_SE_THREADS = 4 wavefronts): ea / eb the thread's exclusive
-// prefix, ta / tb the block's totals
-__device__ __forceinline__ void gf_se_block_scan2(int a, long long b, int* s_a, long long* s_b, int& ea, long long& eb,
-                                                  int& ta, long long& tb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int xa = a;
-  long long xb = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ya = __shfl_up(xa, o);
-    const long long yb = __shfl_up(xb, o);
-    if (lane >= o) { xa += ya; xb += yb; }
-  }
-  if (lane == 63) { s_a[wave] = xa; s_b[wave] = xb; }
-  __syncthreads();
-  int ba = 0; long long bb = 0;
-  ta = 0; tb = 0;
-#pragma unroll
-  for (int w = 0; w < GF_SE_THREADS / 64; ++w) {
-    if (w < wave) { ba += s_a[w]; bb += s_b[w]; }
-    ta += s_a[w]; tb += s_b[w];
-  }
-  ea = ba + xa - a;
-  eb = bb + xb - b;
-  __syncthreads();  // (s_a / s_b are reused by the next scan of the block)
-}
-
-// ---- classify: status per read (GF_SE_NONE / _HIT / _RETRY), retries (reads, bytes) per tile ----
+// ---- classify: status per read (GF_SCAN_NONE / _HIT / _RETRY), retries (reads, bytes) per tile ----
 // st holds GF_SE_TILE bytes per tile (zeros beyond n); too_long counts the reads whose count is GF_COUNT_TOO_LONG.
-__global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_classify(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_se_k_classify(
     const uint8_t* __restrict__ counts, const gf_seqmatch* __restrict__ matches, const int64_t* __restrict__ offsets,
     int64_t n, const uint8_t* __restrict__ rev, int n_genes, uint8_t* __restrict__ st, uint32_t* __restrict__ tile_rc,
     uint32_t* __restrict__ tile_rb, unsigned long long* __restrict__ too_long) {
-  __shared__ int s_a[GF_SE_THREADS / 64];
-  __shared__ long long s_b[GF_SE_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t r0 = (int64_t)blockIdx.x * GF_SE_TILE + (int64_t)threadIdx.x * GF_SE_PER;
   uint8_t c[GF_SE_PER];
   gf_se_bytes16(counts, r0, n, c);
@@ -114,11 +49,11 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_classify(
   uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int k = 0; k < GF_SE_PER; ++k) {
-    uint32_t v = GF_SE_NONE;
+    uint32_t v = GF_SCAN_NONE;
     if (c[k] == 2) {  // mapping.len() == 2: mapable (fusion_mapper.rs:107-115)
       const int64_t r = r0 + k;
-      const bool fwd = gf_se_required_direction(matches[2 * r], matches[2 * r + 1], rev, n_genes);
-      v = fwd ? GF_SE_HIT : GF_SE_RETRY;
+      const bool fwd = gf_scan_required_direction(matches[2 * r], matches[2 * r + 1], rev, n_genes);
+      v = fwd ? GF_SCAN_HIT : GF_SCAN_RETRY;
       if (!fwd) {
         rc += 1;
         rb += offsets[r + 1] - offsets[r];
@@ -131,29 +66,24 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_classify(
   *(uint4*)(st + r0) = make_uint4(w[0], w[1], w[2], w[3]);  // (st is whole tiles long)
   if (tl) atomicAdd(too_long, (unsigned long long)tl);
   int ea, ta; long long eb, tb;
-  gf_se_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
+  gf_scan_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
   if (threadIdx.x == 0) {
     tile_rc[blockIdx.x] = (uint32_t)ta;
     tile_rb[blockIdx.x] = (uint32_t)tb;
   }
 }
 
-// ---- exclusive scan of per-tile totals: block b scans job b (the callers' scans come in pairs: reads and bytes) ----
+// ---- exclusive scan of per-tile totals: block b scans job b (the scans come in pairs: reads and bytes) ----
 // Thread t takes a run of consecutive totals, the runs' sums are scanned across the block, every total's offset is
 // its run's base plus its place in the run.  A batch of 20 M reads has 4 883 tiles: five totals per thread.
-struct GfSeScanJob {
-  const uint32_t* tile_counts;
-  int64_t* tile_offsets;
-  int64_t* d_total;
-};
-struct GfSeScanJobs { GfSeScanJob j[2]; };
+struct GfSeScanJobs { GfScanJob j[2]; };
 
-__global__ __launch_bounds__(GF_SE_SCAN_THREADS) void gf_se_k_scan(GfSeScanJobs jobs, int64_t ntiles) {
+__global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_se_k_scan(GfSeScanJobs jobs, int64_t ntiles) {
   const uint32_t* __restrict__ cnt = jobs.j[blockIdx.x].tile_counts;
   int64_t* __restrict__ off = jobs.j[blockIdx.x].tile_offsets;
-  __shared__ long long s_w[GF_SE_SCAN_THREADS / 64];
+  __shared__ long long s_w[GF_SCAN_TOTALS_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t per = (ntiles + GF_SE_SCAN_THREADS - 1) / GF_SE_SCAN_THREADS;
+  const int64_t per = (ntiles + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
   const int64_t t0 = (int64_t)threadIdx.x * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
   long long mine = 0;
   for (int64_t t = t0; t < t1; ++t) mine += cnt[t];
@@ -166,7 +96,7 @@ __global__ __launch_bounds__(GF_SE_SCAN_THREADS) void gf_se_k_scan(GfSeScanJobs 
   if (lane == 63) s_w[wave] = y;
   __syncthreads();
   long long base = 0, total = 0;
-  for (int w = 0; w < GF_SE_SCAN_THREADS / 64; ++w) {
+  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
     if (w < wave) base += s_w[w];
     total += s_w[w];
   }
@@ -178,40 +108,16 @@ __global__ __launch_bounds__(GF_SE_SCAN_THREADS) void gf_se_k_scan(GfSeScanJobs 
   if (threadIdx.x == 0) *jobs.j[blockIdx.x].d_total = total;
 }
 
-// The reads that the lanes in `mask` have to write, one after the other, every read by all 64 lanes of the
-// wavefront (lane j: bytes j, j + 64, ..): hits and retries are a few per thousand reads, and a lane that copied
-// its own read byte by byte would be alone in its wavefront with one round trip per byte.  revcomp: the read's
-// reverse complement, its qualities reversed.
-__device__ __forceinline__ void gf_se_wave_write(uint64_t mask, const uint8_t* b, const uint8_t* q, int len,
-                                                 long long out, uint8_t* __restrict__ ob, uint8_t* __restrict__ oq,
-                                                 bool revcomp) {
-  const int lane = threadIdx.x & 63;
-  while (mask) {
-    const int l = __builtin_ctzll(mask);
-    mask &= mask - 1;
-    const uint8_t* bb = (const uint8_t*)__shfl((unsigned long long)b, l);
-    const uint8_t* qq = (const uint8_t*)__shfl((unsigned long long)q, l);
-    const int ln = __shfl(len, l);
-    const long long o = __shfl(out, l);
-#pragma unroll 1
-    for (int j = lane; j < ln; j += 64) {
-      const int src = revcomp ? ln - 1 - j : j;
-      ob[o + j] = revcomp ? gf_se_complement(bb[src]) : bb[src];
-      oq[o + j] = qq[src];
-    }
-  }
-}
-
 // ---- retry_write: the reverse complements of the retried reads, back to back, in read order ----
 // r_off[k] = where retry k starts.  A retry beyond the capacities is not written (gf_se_k_retry_tail then empties the
 // whole retry pass and raises the overflow bit).
-__global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_retry_write(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_se_k_retry_write(
     const uint8_t* __restrict__ bases, const uint8_t* __restrict__ quals, const int64_t* __restrict__ offsets, int64_t n,
     const uint8_t* __restrict__ st, const int64_t* __restrict__ tile_off_rc, const int64_t* __restrict__ tile_off_rb,
     int64_t cap_reads, int64_t cap_bytes, int64_t* __restrict__ r_off, uint8_t* __restrict__ r_bases,
     uint8_t* __restrict__ r_quals) {
-  __shared__ int s_a[GF_SE_THREADS / 64];
-  __shared__ long long s_b[GF_SE_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t r0 = (int64_t)blockIdx.x * GF_SE_TILE + (int64_t)threadIdx.x * GF_SE_PER;
   uint8_t v[GF_SE_PER];
   gf_se_bytes16(st, r0, n, v);
@@ -219,18 +125,18 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_retry_write(
   long long rb = 0;
 #pragma unroll
   for (int k = 0; k < GF_SE_PER; ++k)
-    if (v[k] == GF_SE_RETRY) {
+    if (v[k] == GF_SCAN_RETRY) {
       rc += 1;
       rb += offsets[r0 + k + 1] - offsets[r0 + k];
     }
   int ea, ta; long long eb, tb;
-  gf_se_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
+  gf_scan_block_scan2(rc, rb, s_a, s_b, ea, eb, ta, tb);
   if (__ballot(rc != 0) == 0) return;  // (whole wavefronts: the reads are written by all 64 lanes)
   int64_t k_out = tile_off_rc[blockIdx.x] + ea;
   int64_t b_out = tile_off_rb[blockIdx.x] + eb;
 #pragma unroll 1
   for (int k = 0; k < GF_SE_PER; ++k) {
-    const bool mine = v[k] == GF_SE_RETRY;
+    const bool mine = v[k] == GF_SCAN_RETRY;
     const uint8_t* b = nullptr;
     const uint8_t* q = nullptr;
     int len = 0;
@@ -243,7 +149,7 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_retry_write(
       fits = k_out < cap_reads && b_out + len <= cap_bytes;
       if (fits) r_off[k_out] = b_out;
     }
-    gf_se_wave_write(__ballot(fits), b, q, len, (long long)b_out, r_bases, r_quals, true);
+    gf_scan_wave_write(__ballot(fits), b, q, len, (long long)b_out, r_bases, r_quals, true);
     if (mine) {
       k_out += 1;
       b_out += len;
@@ -251,21 +157,12 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_retry_write(
   }
 }
 
-// offsets of the unused retry slots (empty reads at the end of the retry bytes) and the overflow bit.  Over capacity
-// the whole retry pass is emptied (every offset 0): a partly searched batch would look like a result.
+// the unused retry slots emptied, the overflow bit (gf_scan_common.h)
 __global__ void gf_se_k_retry_tail(const int64_t* __restrict__ d_n_retry, const int64_t* __restrict__ d_retry_bytes,
                                    int64_t cap_reads, int64_t cap_bytes, int64_t* __restrict__ r_off,
                                    int64_t* __restrict__ totals) {
-  const int64_t nr = *d_n_retry, nb = *d_retry_bytes;
-  const bool over = nr > cap_reads || nb > cap_bytes;
-  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= cap_reads; k += (int64_t)gridDim.x * blockDim.x) {
-    if (over) r_off[k] = 0;
-    else if (k >= nr) r_off[k] = nb;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    totals[3] = nr;
-    if (over) totals[4] |= 1;
-  }
+  gf_scan_retry_tail(d_n_retry, d_retry_bytes, cap_reads, cap_bytes, r_off, totals,
+                     (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // ---- final: the hits of the batch in read order.  WRITE = false: hits and their bytes per tile; true: the records,
@@ -287,20 +184,20 @@ struct GfSeFinalIn {
 };
 
 template <bool WRITE>
-__global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_final(
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_se_k_final(
     GfSeFinalIn F, int64_t n, int64_t read_id_base, uint32_t* __restrict__ tile_hc, uint32_t* __restrict__ tile_hb,
     const int64_t* __restrict__ tile_off_hc, const int64_t* __restrict__ tile_off_hb, gf_pair_hit* __restrict__ hits,
     int64_t hits_cap, uint8_t* __restrict__ out_bases, uint8_t* __restrict__ out_quals, int64_t bytes_cap) {
-  __shared__ int s_a[GF_SE_THREADS / 64];
-  __shared__ long long s_b[GF_SE_THREADS / 64];
+  __shared__ int s_a[GF_SCAN_THREADS / 64];
+  __shared__ long long s_b[GF_SCAN_THREADS / 64];
   const int64_t r0 = (int64_t)blockIdx.x * GF_SE_TILE + (int64_t)threadIdx.x * GF_SE_PER;
   uint8_t v[GF_SE_PER];
   gf_se_bytes16(F.st, r0, n, v);
   int rc = 0;
 #pragma unroll
-  for (int k = 0; k < GF_SE_PER; ++k) rc += v[k] == GF_SE_RETRY;
+  for (int k = 0; k < GF_SE_PER; ++k) rc += v[k] == GF_SCAN_RETRY;
   int er, tr; long long e0, t0;
-  gf_se_block_scan2(rc, 0, s_a, s_b, er, e0, tr, t0);
+  gf_scan_block_scan2(rc, 0, s_a, s_b, er, e0, tr, t0);
   // slot[k] >= 0: the hit is on the reverse complement in retry slot slot[k]; hit bit k: read r0 + k is a hit
   int64_t slot0 = F.tile_off_rc[blockIdx.x] + er;
   uint32_t hit = 0, on_rc = 0;
@@ -308,11 +205,11 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_final(
   long long hb = 0;
 #pragma unroll
   for (int k = 0; k < GF_SE_PER; ++k) {
-    bool h = v[k] == GF_SE_HIT;
-    if (v[k] == GF_SE_RETRY) {
+    bool h = v[k] == GF_SCAN_HIT;
+    if (v[k] == GF_SCAN_RETRY) {
       const int64_t s = slot0++;
       if (s < F.cap_reads && F.cR[s] == 2 &&
-          gf_se_required_direction(F.mR[2 * s], F.mR[2 * s + 1], F.rev, F.n_genes)) {
+          gf_scan_required_direction(F.mR[2 * s], F.mR[2 * s + 1], F.rev, F.n_genes)) {
         h = true;
         on_rc |= 1u << k;
       }
@@ -324,7 +221,7 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_final(
     }
   }
   int ea, ta; long long eb, tb;
-  gf_se_block_scan2(hc, hb, s_a, s_b, ea, eb, ta, tb);
+  gf_scan_block_scan2(hc, hb, s_a, s_b, ea, eb, ta, tb);
   if (!WRITE) {
     if (threadIdx.x == 0) {
       tile_hc[blockIdx.x] = (uint32_t)ta;
@@ -341,7 +238,7 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_final(
     const bool mine = (hit >> k) & 1u;
     const bool rcm = (on_rc >> k) & 1u;
     const int64_t my_slot = slot;
-    if (v[k] == GF_SE_RETRY) slot += 1;
+    if (v[k] == GF_SCAN_RETRY) slot += 1;
     const uint8_t* b = nullptr;
     const uint8_t* q = nullptr;
     int len = 0;
@@ -373,7 +270,7 @@ __global__ __launch_bounds__(GF_SE_THREADS) void gf_se_k_final(
       }
       bytes_fit = b_out + len <= bytes_cap;
     }
-    gf_se_wave_write(__ballot(bytes_fit), b, q, len, (long long)b_out, out_bases, out_quals, false);
+    gf_scan_wave_write(__ballot(bytes_fit), b, q, len, (long long)b_out, out_bases, out_quals, false);
     if (mine) {
       k_out += 1;
       b_out += len;

@@ -1,54 +1,16 @@
 // libgfse.so: the single-end scan (include/gf_single_end.h) on top of libgfmatch.so's public ABI.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <string>
-
 #include "gf_se_kernels.h"
+#include "gf_scan_host.h"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define GF_SE_HIP(x)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (x);                                                              \
-    if (e_ != hipSuccess) return fail(GF_ERR_HIP, std::string(#x ": ") + hipGetErrorString(e_)); \
-  } while (0)
-
-// a gfmatch call failed: its message becomes ours
-int passed_on(int rc) { return fail(rc, std::string("gf_map_reads_device: ") + gf_last_error()); }
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    else ok = true, prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-// The workspace, carved in 256-byte aligned pieces from a 256-byte aligned base.
+// The workspace (scalar [4] of the retry part: the too-long reads).
 struct Layout {
-  int64_t n = 0, R = 0, Rb = 0, ntiles = 0;
-  size_t o_cnt = 0, o_st = 0, o_m1 = 0, o_tc = 0, o_to = 0, o_scal = 0, o_roff = 0, o_rb = 0, o_rq = 0, o_cR = 0, o_mR = 0;
+  int64_t n = 0, ntiles = 0;
+  size_t o_cnt = 0, o_st = 0, o_m1 = 0, o_tc = 0, o_to = 0;
+  RetryWork retry;
   size_t bytes = 0;
 };
-
-size_t take(size_t& off, size_t bytes) {
-  const size_t o = off;
-  off += (bytes + 255) & ~(size_t)255;
-  return o;
-}
 
 int64_t resolve_retry_cap(int64_t n, int64_t retry_cap) {
   const int64_t r = retry_cap <= 0 ? gf_se_retry_capacity(n) : retry_cap;
@@ -58,8 +20,6 @@ int64_t resolve_retry_cap(int64_t n, int64_t retry_cap) {
 Layout layout(int64_t n, int32_t max_read_len, int64_t retry_cap) {
   Layout L;
   L.n = n;
-  L.R = resolve_retry_cap(n, retry_cap);
-  L.Rb = L.R * (int64_t)std::max(max_read_len, 1);
   L.ntiles = (n + GF_SE_TILE - 1) / GF_SE_TILE;
   size_t off = 0;
   L.o_cnt = take(off, (size_t)n);                                 // first pass: counts
@@ -67,13 +27,8 @@ Layout layout(int64_t n, int32_t max_read_len, int64_t retry_cap) {
   L.o_m1 = take(off, (size_t)n * 2 * sizeof(gf_seqmatch));        // first pass: matches
   L.o_tc = take(off, (size_t)L.ntiles * 2 * sizeof(uint32_t));    // two uint32 per tile: reads, bytes
   L.o_to = take(off, (size_t)L.ntiles * 4 * sizeof(int64_t));     // their offsets: retries (2), hits (2)
-  L.o_scal = take(off, 256);                                      // [0] retries, [1] retry bytes, [2] hits, [3] hit bytes, [4] too long
-  L.o_roff = take(off, ((size_t)L.R + 1) * sizeof(int64_t));
-  // the retry reads: the mapping kernels read whole 16-byte chunks around a span (gfmatch.h), inside this workspace
-  L.o_rb = take(off, (size_t)L.Rb + 64);
-  L.o_rq = take(off, (size_t)L.Rb + 64);
-  L.o_cR = take(off, (size_t)L.R);
-  L.o_mR = take(off, (size_t)L.R * 2 * sizeof(gf_seqmatch));
+  const int64_t R = resolve_retry_cap(n, retry_cap);
+  L.retry.carve(off, R, R * (int64_t)std::max(max_read_len, 1));
   L.bytes = off + 256;  // (room to align the caller's base)
   return L;
 }
@@ -81,9 +36,9 @@ Layout layout(int64_t n, int32_t max_read_len, int64_t retry_cap) {
 void launch_scan(hipStream_t st, int64_t ntiles, const uint32_t* c0, int64_t* o0, int64_t* t0, const uint32_t* c1,
                  int64_t* o1, int64_t* t1) {
   GfSeScanJobs J;
-  J.j[0] = GfSeScanJob{c0, o0, t0};
-  J.j[1] = GfSeScanJob{c1, o1, t1};
-  hipLaunchKernelGGL(gf_se_k_scan, dim3(2), dim3(GF_SE_SCAN_THREADS), 0, st, J, ntiles);
+  J.j[0] = GfScanJob{c0, o0, t0};
+  J.j[1] = GfScanJob{c1, o1, t1};
+  hipLaunchKernelGGL(gf_se_k_scan, dim3(2), dim3(GF_SCAN_TOTALS_THREADS), 0, st, J, ntiles);
 }
 
 }  // namespace
@@ -123,15 +78,16 @@ int gf_se_scan_device(const gf_index* idx, const void* d_bases, const void* d_qu
     return fail(GF_ERR_CAPACITY, "workspace smaller than gf_se_workspace_bytes");
   gf_index_info info;
   const int irc = gf_index_info_get(idx, &info);
-  if (irc != GF_OK) return fail(irc, std::string("gf_index_info_get: ") + gf_last_error());
+  if (irc != GF_OK) return passed_on("gf_index_info_get", irc);
   DeviceGuard guard(info.device);
   if (!guard.ok) return fail(GF_ERR_HIP, "cannot select the index's device");
   hipStream_t st = (hipStream_t)stream;
   int64_t* totals = (int64_t*)d_totals;
-  GF_SE_HIP(hipMemsetAsync(totals, 0, 8 * sizeof(int64_t), st));
+  GF_SCAN_HIP(hipMemsetAsync(totals, 0, 8 * sizeof(int64_t), st));
   if (n == 0) return GF_OK;
 
-  uint8_t* wp = (uint8_t*)(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
+  const RetryWork& W = L.retry;
+  uint8_t* wp = aligned(d_workspace);
   uint8_t* cnt = wp + L.o_cnt;
   uint8_t* stt = wp + L.o_st;
   gf_seqmatch* m1 = (gf_seqmatch*)(wp + L.o_m1);
@@ -139,48 +95,48 @@ int gf_se_scan_device(const gf_index* idx, const void* d_bases, const void* d_qu
   uint32_t* tcB = tcA + L.ntiles;
   int64_t* toRC = (int64_t*)(wp + L.o_to);
   int64_t *toRB = toRC + L.ntiles, *toHC = toRB + L.ntiles, *toHB = toHC + L.ntiles;
-  int64_t* scal = (int64_t*)(wp + L.o_scal);
-  int64_t* r_off = (int64_t*)(wp + L.o_roff);
-  uint8_t *rb = wp + L.o_rb, *rq = wp + L.o_rq, *cR = wp + L.o_cR;
-  gf_seqmatch* mR = (gf_seqmatch*)(wp + L.o_mR);
+  int64_t* scal = (int64_t*)(wp + W.o_scal);
+  int64_t* r_off = (int64_t*)(wp + W.o_roff);
+  uint8_t *rb = wp + W.o_rb, *rq = wp + W.o_rq, *cR = wp + W.o_cR;
+  gf_seqmatch* mR = (gf_seqmatch*)(wp + W.o_mR);
   const uint8_t* rev = (const uint8_t*)d_gene_reversed;
   const unsigned grid = (unsigned)L.ntiles;
-  GF_SE_HIP(hipMemsetAsync(scal, 0, 256, st));
+  GF_SCAN_HIP(hipMemsetAsync(scal, 0, 256, st));
 
   // 1. every read as it is
   int rc = gf_map_reads_device(idx, d_bases, d_offsets, n, std::max(max_read_len, 1), cnt, m1, st);
-  if (rc != GF_OK) return passed_on(rc);
+  if (rc != GF_OK) return passed_on("gf_map_reads_device", rc);
   // 2. hit / retry / neither, and the retries per tile
-  hipLaunchKernelGGL(gf_se_k_classify, dim3(grid), dim3(GF_SE_THREADS), 0, st, (const uint8_t*)cnt,
+  hipLaunchKernelGGL(gf_se_k_classify, dim3(grid), dim3(GF_SCAN_THREADS), 0, st, (const uint8_t*)cnt,
                      (const gf_seqmatch*)m1, (const int64_t*)d_offsets, n, rev, (int)n_genes, stt, tcA, tcB,
                      (unsigned long long*)(scal + 4));
   // 3. where each tile's retries go
   launch_scan(st, L.ntiles, tcA, toRC, scal + 0, tcB, toRB, scal + 1);
   // 4. the reverse complements, back to back; unused slots empty; over capacity the pass is emptied
-  hipLaunchKernelGGL(gf_se_k_retry_write, dim3(grid), dim3(GF_SE_THREADS), 0, st, (const uint8_t*)d_bases,
+  hipLaunchKernelGGL(gf_se_k_retry_write, dim3(grid), dim3(GF_SCAN_THREADS), 0, st, (const uint8_t*)d_bases,
                      (const uint8_t*)d_quals, (const int64_t*)d_offsets, n, (const uint8_t*)stt, (const int64_t*)toRC,
-                     (const int64_t*)toRB, L.R, L.Rb, r_off, rb, rq);
-  hipLaunchKernelGGL(gf_se_k_retry_tail, dim3((unsigned)std::min<int64_t>((L.R + 256) / 256, 1024)), dim3(256), 0, st,
-                     (const int64_t*)(scal + 0), (const int64_t*)(scal + 1), L.R, L.Rb, r_off, totals);
-  GF_SE_HIP(hipGetLastError());
+                     (const int64_t*)toRB, W.R, W.Rb, r_off, rb, rq);
+  hipLaunchKernelGGL(gf_se_k_retry_tail, dim3(retry_tail_blocks(W.R)), dim3(256), 0, st,
+                     (const int64_t*)(scal + 0), (const int64_t*)(scal + 1), W.R, W.Rb, r_off, totals);
+  GF_SCAN_HIP(hipGetLastError());
   // 5. the retry slots (the number of retries is on the device: every slot is mapped, the empty ones give count 0)
-  rc = gf_map_reads_device(idx, rb, r_off, L.R, std::max(max_read_len, 1), cR, mR, st);
-  if (rc != GF_OK) return passed_on(rc);
+  rc = gf_map_reads_device(idx, rb, r_off, W.R, std::max(max_read_len, 1), cR, mR, st);
+  if (rc != GF_OK) return passed_on("gf_map_reads_device", rc);
   // 6. the hits in read order: count per tile, scan, write; the totals
   GfSeFinalIn F;
   F.bases = (const uint8_t*)d_bases; F.quals = (const uint8_t*)d_quals; F.offsets = (const int64_t*)d_offsets;
   F.m1 = m1; F.st = stt; F.tile_off_rc = toRC; F.cR = cR; F.mR = mR; F.r_off = r_off; F.r_bases = rb; F.r_quals = rq;
-  F.cap_reads = L.R; F.rev = rev; F.n_genes = (int)n_genes;
-  hipLaunchKernelGGL(gf_se_k_final<false>, dim3(grid), dim3(GF_SE_THREADS), 0, st, F, n, read_id_base, tcA, tcB,
+  F.cap_reads = W.R; F.rev = rev; F.n_genes = (int)n_genes;
+  hipLaunchKernelGGL(gf_se_k_final<false>, dim3(grid), dim3(GF_SCAN_THREADS), 0, st, F, n, read_id_base, tcA, tcB,
                      (const int64_t*)nullptr, (const int64_t*)nullptr, (gf_pair_hit*)nullptr, (int64_t)0,
                      (uint8_t*)nullptr, (uint8_t*)nullptr, (int64_t)0);
   launch_scan(st, L.ntiles, tcA, toHC, scal + 2, tcB, toHB, scal + 3);
-  hipLaunchKernelGGL(gf_se_k_final<true>, dim3(grid), dim3(GF_SE_THREADS), 0, st, F, n, read_id_base,
+  hipLaunchKernelGGL(gf_se_k_final<true>, dim3(grid), dim3(GF_SCAN_THREADS), 0, st, F, n, read_id_base,
                      (uint32_t*)nullptr, (uint32_t*)nullptr, (const int64_t*)toHC, (const int64_t*)toHB,
                      (gf_pair_hit*)d_hits, hits_cap, (uint8_t*)d_hit_bases, (uint8_t*)d_hit_quals, hit_bytes_cap);
   hipLaunchKernelGGL(gf_se_k_totals, dim3(1), dim3(1), 0, st, (const int64_t*)(scal + 2), (const int64_t*)(scal + 3),
                      (const unsigned long long*)(scal + 4), hits_cap, hit_bytes_cap, totals);
-  GF_SE_HIP(hipGetLastError());
+  GF_SCAN_HIP(hipGetLastError());
   return GF_OK;
 }
 

@@ -1,7 +1,7 @@
 """``SingleEndScanner::scan_single_end`` (src/core/sescanner.rs:183-205) for a batch of reads resident in HBM, one
 asynchronous call: ``gf_se_scan_device`` of libgfse.so (include/gf_single_end.h).
 
-libgfse.so is a library of its own on top of libgfmatch.so's public C ABI (genefuserust_amd/se_csrc/); it is loaded
+libgfse.so is a library of its own on top of libgfmatch.so's public C ABI (genefuserust_amd/scan_csrc/); it is loaded
 after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this tree.  The result is a ``PairScan`` in the
 format of ``gf_scan_pairs_device`` (source 1 = "r1"), so ``PairScan.download``, ``finish_pair_hits`` and
 ``finish_pair_hits_device`` take it unchanged.  No CPU fallback: without the libraries and a GPU every call raises.
@@ -15,7 +15,7 @@ from typing import Optional
 from . import _lib
 from ._lib import GF_ERR_NO_DEVICE, GF_ERR_READ_TOO_LONG, GfError
 from .indexer import Indexer
-from .read_pair import PairScan
+from .read_pair import PairScan, companion_scan, gene_reversed_device
 
 SE_LIB_PATH = os.path.join(_lib._HERE, "libgfse.so")
 
@@ -28,16 +28,7 @@ def lib() -> C.CDLL:
     global _se
     if _se is not None:
         return _se
-    _lib.lib()
-    own = os.path.join(_lib._HERE, "libgfmatch.so")
-    if os.path.realpath(_lib.LIB_PATH) != os.path.realpath(own):
-        raise ImportError("GFMATCH_LIB=%s: libgfse.so links against %s; the single-end scan does not mix two builds"
-                          % (_lib.LIB_PATH, own))
-    if not os.path.exists(SE_LIB_PATH):
-        raise ImportError(
-            "libgfse.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The single-end scan has no CPU fallback." % SE_LIB_PATH)
-    L = C.CDLL(SE_LIB_PATH)
+    L = _lib.load_companion(SE_LIB_PATH, "single-end scan")
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.gf_se_retry_capacity.argtypes = [i64]
     L.gf_se_retry_capacity.restype = i64
@@ -56,18 +47,6 @@ def check(rc: int) -> int:
     if rc < 0:
         raise GfError(rc, lib().gf_se_last_error().decode("utf-8", "replace"))
     return rc
-
-
-def _gene_reversed(indexer: Indexer, dev):
-    """Fusion::is_reversed() per gene as a device tensor, uploaded once per index and device."""
-    import torch
-    from .fusion_mapper import FusionMapper
-    cached = getattr(indexer, "_se_gene_rev", None)
-    if cached is None or cached.device != dev:
-        rev = FusionMapper(indexer)._rev   # (uint8, at least one element)
-        cached = torch.from_numpy(rev.copy()).to(dev)
-        indexer._se_gene_rev = cached
-    return cached
 
 
 def scan_single_device(indexer: Indexer, bases, quals, offsets, max_read_len: int, read_id_base: int = 0,
@@ -89,29 +68,17 @@ def scan_single_device(indexer: Indexer, bases, quals, offsets, max_read_len: in
     L = lib()
     n = offsets.numel() - 1
     dev = bases.device
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     hits_cap = max(1024, n // 16) if hits_cap is None else int(hits_cap)
     bytes_cap = hits_cap * max(int(max_read_len), 1) if bytes_cap is None else int(bytes_cap)
-    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
-    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    totals = torch.zeros(8, dtype=torch.int64, device=dev)
     ws_bytes = int(L.gf_se_workspace_bytes(n, int(max_read_len), int(retry_cap)))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    rev = _gene_reversed(indexer, dev)
-    n_genes = len(indexer.m_fusions)
-    check(L.gf_se_scan_device(indexer._handle(), bases.data_ptr(), quals.data_ptr(), offsets.data_ptr(), bases.numel(),
-                              n, int(max_read_len), rev.data_ptr(), n_genes, int(read_id_base), int(retry_cap),
-                              ws.data_ptr(), ws_bytes, hits.data_ptr(), hits_cap, hb.data_ptr(), hq.data_ptr(), bytes_cap,
-                              totals.data_ptr(), st))
-    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
-    if stream is not None:
-        ext = torch.cuda.ExternalStream(stream, device=dev)
-        ws.record_stream(ext)
-        if check_lengths:
-            ext.synchronize()
+    head = (indexer._handle(), bases.data_ptr(), quals.data_ptr(), offsets.data_ptr(), bases.numel(), n,
+            int(max_read_len), gene_reversed_device(indexer, dev).data_ptr(), len(indexer.m_fusions), int(read_id_base),
+            int(retry_cap))
+    scan = companion_scan(check, L.gf_se_scan_device, head, dev, ws_bytes, hits_cap, bytes_cap, stream)
     if check_lengths:
-        too_long = int(totals[5].item())
+        if stream is not None:
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        too_long = int(scan.totals[5].item())
         if too_long:
             raise GfError(GF_ERR_READ_TOO_LONG, "%d reads are longer than max_read_len = %d" % (too_long, max_read_len))
-    return PairScan(hits, hb, hq, totals)
+    return scan

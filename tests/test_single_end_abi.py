@@ -110,10 +110,10 @@ def test_scan_single_device_raises_without_a_device():
 
 
 def test_gfmatch_sources_untouched():
-    """The profiled library stays byte-identical: the single-end scan lives in se_csrc/ and gf_single_end.h."""
+    """The profiled library's sources and the three public headers stay byte-identical."""
     r = subprocess.run(["git", "-C", ROOT, "rev-parse", "--verify", "-q", "main"], capture_output=True, text=True)
     if r.returncode != 0:
         pytest.skip("no main branch in this checkout")
-    d = subprocess.run(["git", "-C", ROOT, "diff", "main", "--", "genefuserust_amd/csrc", "include/gfmatch.h"],
-                       capture_output=True, text=True)
+    d = subprocess.run(["git", "-C", ROOT, "diff", "main", "--", "genefuserust_amd/csrc", "include/gfmatch.h",
+                        "include/gf_single_end.h", "include/gf_multi_csv.h"], capture_output=True, text=True)
     assert d.returncode == 0 and d.stdout == ""
