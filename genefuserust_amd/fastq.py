@@ -106,6 +106,11 @@ class FastqReader:
         with open(self.m_filename, "rb") as f:
             return f.read()
 
+    def open_stream(self) -> "FastqByteStream":
+        """The plain text of the file as a byte source for the streamed scans (scan_stream.py): ``readinto`` hands
+        out the bytes ``text()`` returns, piece by piece, without ever holding the whole of them."""
+        return FastqByteStream(self.m_filename, self.m_zipped)
+
     def read_all_device(self, indexer: Indexer) -> Tuple[FastqBatch, bytes]:
         """(batch, host text).  The host text is kept for names and strand lines."""
         import torch
@@ -114,6 +119,27 @@ class FastqReader:
         d = torch.from_numpy(np.frombuffer(t, dtype=np.uint8).copy()).to(dev) if t else \
             torch.empty(0, dtype=torch.uint8, device=dev)
         return fastq_cut_device(indexer, d), t
+
+
+class FastqByteStream:
+    """A FASTQ file as a byte source: ``readinto(memoryview) -> int``, 0 at the end.  A zipped file is inflated as it is
+    read (``gzip.open``: concatenated members too, like MultiGzDecoder); ``name`` is the file's, for messages."""
+
+    def __init__(self, file_name: str, zipped: bool):
+        self.name = file_name
+        self._f = gzip.open(file_name, "rb") if zipped else open(file_name, "rb", buffering=0)
+
+    def readinto(self, mv) -> int:
+        return self._f.readinto(mv) or 0
+
+    def close(self) -> None:
+        self._f.close()
+
+    def __enter__(self) -> "FastqByteStream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
 
 
 def record_lines(batch: FastqBatch, text: bytes, i: int) -> Tuple[bytes, bytes, bytes, bytes]:

@@ -1,0 +1,107 @@
+"""The names of the reads a scan matched, gathered on the device: ``gf_hn_names_device`` of libgfnames.so
+(include/gf_hit_names.h).
+
+A ``ReadMatch`` carries the name of the read it was found on.  The whole-file scans cut it from the host copy of the
+FASTQ text (``fastq.record_lines``); here the name lines of the hit records are copied out of the text while it is still
+in HBM, in one asynchronous call, so that a streamed scan can drop a chunk's text as soon as the chunk is scanned
+(scan_stream.py).  libgfnames.so is a library of its own on top of libgfmatch.so's public C ABI
+(genefuserust_amd/scan_csrc/); it is loaded after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this
+tree.  No CPU fallback: without the libraries and a GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import List, NamedTuple, Optional
+
+from . import _lib
+from ._lib import GF_ERR_CAPACITY, GF_ERR_NO_DEVICE, GfError
+from .indexer import Indexer
+from .read_pair import PairScan
+
+HN_LIB_PATH = os.path.join(_lib._HERE, "libgfnames.so")
+
+_hn = None
+
+
+def lib() -> C.CDLL:
+    """Load libgfnames.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names
+    another libgfmatch.so than the one libgfnames.so links against (two builds of the mapping in one process)."""
+    global _hn
+    if _hn is not None:
+        return _hn
+    L = _lib.load_companion(HN_LIB_PATH, "hit-name gather")
+    vp, i64 = C.c_void_p, C.c_int64
+    L.gf_hn_workspace_bytes.argtypes = [i64]
+    L.gf_hn_workspace_bytes.restype = i64
+    L.gf_hn_names_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp,
+                                     vp]
+    L.gf_hn_names_device.restype = C.c_int
+    L.gf_hn_last_error.argtypes = []
+    L.gf_hn_last_error.restype = C.c_char_p
+    _hn = L
+    return L
+
+
+def check(rc: int) -> int:
+    if rc < 0:
+        raise GfError(rc, lib().gf_hn_last_error().decode("utf-8", "replace"))
+    return rc
+
+
+class HitNames(NamedTuple):
+    """What gf_hn_names_device leaves in HBM: ``names`` uint8[names_cap] (the names back to back), ``offsets``
+    int64[hits_cap + 1], ``totals`` int64[4] (names, their bytes, overflow bit, records without a name line)."""
+    names: "object"
+    offsets: "object"
+    totals: "object"
+
+    def download(self) -> List[bytes]:
+        """Synchronises.  The names in record order; ``GfError(GF_ERR_CAPACITY)`` when ``names_cap`` was too small
+        (the message says how many bytes are needed)."""
+        n, nbytes, over, _ = (int(x) for x in self.totals.cpu())
+        if over:
+            raise GfError(GF_ERR_CAPACITY, "the names take %d bytes, names_cap is %d" % (nbytes, self.names.numel()))
+        off = self.offsets[:n + 1].cpu().numpy()
+        buf = self.names[:nbytes].cpu().numpy().tobytes()
+        return [buf[off[k]:off[k + 1]] for k in range(n)]
+
+
+def hit_names_device(indexer: Indexer, scan: PairScan, l_text, l_batch, r_text=None, r_batch=None,
+                     pair_id_base: int = 0, names_cap: Optional[int] = None, stream=None) -> HitNames:
+    """The name lines of the records of ``scan``, asynchronously.  ``l_text`` (uint8 device tensor) is the FASTQ text
+    the scanned records were cut from and ``l_batch`` its ``FastqBatch`` (for the newline index); ``r_text`` /
+    ``r_batch`` the same for R2, ``None`` for single-end input.  ``pair_id_base`` is what the scan was given: record k
+    names FASTQ record ``pair_id - pair_id_base`` — of R2 when its ``source`` is 2, else of R1 — and gets what
+    ``fastq.record_lines(batch, text, i)[0]`` returns.  ``names_cap``: bytes for the names (default: 64 per record
+    capacity; ``totals`` says when that was too small, and how much is needed)."""
+    import torch
+    tensors = [scan.hits, scan.totals, l_text, l_batch.nl_pos] + ([] if r_text is None else [r_text, r_batch.nl_pos])
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GfError(GF_ERR_NO_DEVICE, "hit_names_device takes device tensors (there is no CPU fallback)")
+    assert l_text.dtype == torch.uint8 and l_text.is_contiguous() and l_batch.nl_pos.dtype == torch.int64
+    assert l_batch.nl_pos.is_contiguous() and l_batch.nl_pos.numel() >= l_batch.n_newlines
+    if r_text is not None:
+        assert r_text.dtype == torch.uint8 and r_text.is_contiguous() and r_batch.nl_pos.dtype == torch.int64
+        assert r_batch.nl_pos.is_contiguous() and r_batch.nl_pos.numel() >= r_batch.n_newlines
+    L = lib()
+    dev = l_text.device
+    hits_cap = int(scan.hits.shape[0])
+    names_cap = 64 * hits_cap if names_cap is None else int(names_cap)
+    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    ws_bytes = int(L.gf_hn_workspace_bytes(hits_cap))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    names = torch.empty(max(names_cap, 1), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(hits_cap + 1, dtype=torch.int64, device=dev)
+    totals = torch.zeros(4, dtype=torch.int64, device=dev)
+    right = (None, 0, None, 0) if r_text is None else (r_text.data_ptr(), r_text.numel(), r_batch.nl_pos.data_ptr(),
+                                                       int(r_batch.n_newlines))
+    check(L.gf_hn_names_device(indexer._handle(), scan.hits.data_ptr(), scan.totals.data_ptr(), hits_cap,
+                               int(pair_id_base), l_text.data_ptr(), l_text.numel(), l_batch.nl_pos.data_ptr(),
+                               int(l_batch.n_newlines), *right, ws.data_ptr(), ws_bytes, names.data_ptr(), names_cap,
+                               offsets.data_ptr(), totals.data_ptr(), st))
+    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the call)
+    if stream is not None:
+        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return HitNames(names, offsets, totals)

@@ -261,20 +261,27 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
 
 def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
-                settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = ""):
+                settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
+                chunk_bytes: int = None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
-    gives ``scan_multi_csv_report``'s list."""
+    gives ``scan_multi_csv_report``'s list.  ``chunk_bytes`` streams the FASTQ files of the single-CSV scanners
+    (``scan.scan_pair_end_files``); multi-CSV mode keeps its reads resident, as the reference does, and raises
+    ``ValueError`` for it."""
     from . import scan
     if _rust_stem_ext(fusion_file)[2] == "csv":
         if read2_file:
-            results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings)
+            results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings,
+                                                          chunk_bytes=chunk_bytes)
         else:
-            results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings)
+            results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings,
+                                                            chunk_bytes=chunk_bytes)
         if json_file:
             with open(json_file, "w") as f:
                 f.write(report_json(results, command, version, time, settings))
         return results, counters
+    if chunk_bytes is not None:
+        raise ValueError("chunk_bytes: multi-CSV mode scans resident reads once per CSV and does not stream them")
     return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
                                  version, time)

@@ -22,18 +22,33 @@ from .read_pair import finish_pair_hits, scan_pairs_device
 
 def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                         deletion_threshold: int = 50, _keep: dict = None,
-                        remove_alignables: bool = False) -> Tuple[List[ReadMatch], dict]:
+                        remove_alignables: bool = False, chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (for a merged read the R1 name with the " merged_diff_N" suffix of
-    read.rs:372)."""
+    read.rs:372).
+
+    ``chunk_bytes``: None reads both files whole.  With a value they are streamed in chunks of that many bytes of
+    plain text (scan_stream.scan_pair_source_stream: read, gunzipped and uploaded while the previous chunk is
+    scanned, the names of the matched reads gathered on the device), so that neither the host nor the device ever
+    holds a file; the matches and counters are the same, and the counters add ``chunks``."""
     ref = FastaReader(ref_file, True)
     ref.read_all()
     fusions = Fusion.parse_csv(fusion_csv)
     ix = Indexer(ref.m_all_contigs, fusions, device)
     ix.make_index()
     try:
-        (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
         mapper = FusionMapper(ix)
+        if chunk_bytes is not None:
+            found, counters = _pair_end_streamed(ix, mapper, read1_file, read2_file, chunk_bytes)
+            kept, removed = mapper.filter_matches(found, deletion_threshold)
+            if remove_alignables:
+                kept, removed["alignables"] = mapper.remove_alignables(kept)
+            chunks = counters.pop("chunks")
+            counters = {**counters, **removed, "chunks": chunks}
+            if _keep is not None:
+                _keep.update(fusions=fusions, fusion_seq=list(ix.m_fusion_seq))
+            return FusionMapper.sort_matches(kept), counters
+        (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
         # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
         n = l.n_records
         max_len = max(l.max_read_len(), r.max_read_len(), 1)
@@ -63,16 +78,54 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
         ix.close()
 
 
+def _finish_streamed(mapper: FusionMapper, chunks, count_key: str) -> Tuple[List[ReadMatch], dict]:
+    """The tail of a streamed scan: ``finish_pair_hits`` per chunk, each match named from the chunk's device-gathered
+    names.  (matches in push order, counters before the filters)."""
+    found: List[ReadMatch] = []
+    counters = {count_key: 0, "matches_before_filtering": 0, "merged_pairs": 0, "retried_reads": 0, "chunks": 0}
+    code = {"merged": 0, "r1": 1, "r2": 2}
+    for rec, hb, hq, names, tot in chunks:
+        # a match on R2 (or its reverse complement) carries R2's name; anything else R1's: the names call chose already
+        name_of = {(int(h["pair_id"]), int(h["source"])): nm for h, nm in zip(rec, names)}
+        for i, m in finish_pair_hits(mapper, rec, hb, hq):
+            m.m_name = name_of[(i, code[m.m_source])]
+            if m.m_source == "merged":
+                m.m_name += b" merged_diff_%d" % m.m_merge_diff
+            found.append(m)
+        for k in (count_key, "merged_pairs", "retried_reads"):
+            counters[k] += tot[k]
+        counters["chunks"] += 1
+    counters["matches_before_filtering"] = len(found)
+    return found, counters
+
+
+def _pair_end_streamed(ix: Indexer, mapper: FusionMapper, read1_file: str, read2_file: str,
+                       chunk_bytes: int) -> Tuple[List[ReadMatch], dict]:
+    from .scan_stream import scan_pair_source_stream
+    with FastqReader(read1_file).open_stream() as s1, FastqReader(read2_file).open_stream() as s2:
+        return _finish_streamed(mapper, scan_pair_source_stream(ix, s1, s2, chunk_bytes, max_read_len=None), "pairs")
+
+
+def _single_end_streamed(ix: Indexer, mapper: FusionMapper, read1_file: str,
+                         chunk_bytes: int) -> Tuple[List[ReadMatch], dict]:
+    from .scan_stream import scan_single_text_stream
+    with FastqReader(read1_file).open_stream() as s1:
+        found, counters = _finish_streamed(mapper, scan_single_text_stream(ix, s1, chunk_bytes, max_read_len=None),
+                                           "reads")
+    counters.pop("merged_pairs")
+    return found, counters
+
+
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
-                         settings: Settings = None) -> Tuple[List[FusionResult], dict]:
+                         settings: Settings = None, chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` of fusion_result.py turn the list into
-    the reference's stdout block and JSON file."""
+    the reference's stdout block and JSON file.  ``chunk_bytes``: see ``scan_pair_end_files``."""
     settings = settings or Settings()
     keep: dict = {}
     kept, counters = scan_pair_end_files(ref_file, fusion_csv, read1_file, read2_file, device,
-                                         settings.deletion_threshold, keep)
+                                         settings.deletion_threshold, keep, chunk_bytes=chunk_bytes)
     groups = group_and_sort(kept, len(keep["fusions"]))
     results = cluster_matches(groups, keep["fusions"], keep["fusion_seq"], settings)
     counters["fusions"] = len(results)
@@ -81,22 +134,37 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
 
 def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                           deletion_threshold: int = 50, _keep: dict = None,
-                          route: str = "device") -> Tuple[List[ReadMatch], dict]:
+                          route: str = "device", chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
     ``route="device"``: the records stay in HBM from the FASTQ cut to the hit list — one ``gf_se_scan_device`` call
     (single_end.py), the tail by ``finish_pair_hits``; the counters add ``retried_reads``.  ``route="host"``: the
     records go to the host and through ``FusionMapper.scan_single_end`` (two mapping calls over host buffers, the tail
-    per matched read).  Both give the same matches and counters."""
+    per matched read).  Both give the same matches and counters.
+
+    ``chunk_bytes`` (device route only): None reads the file whole; with a value it is streamed in chunks of that many
+    bytes of plain text (scan_stream.scan_single_text_stream), as in ``scan_pair_end_files``; the counters add
+    ``chunks``."""
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
+    if chunk_bytes is not None and route != "device":
+        raise ValueError("chunk_bytes streams the file through the device route; route=%r reads it whole" % (route,))
     ref = FastaReader(ref_file, True)
     ref.read_all()
     fusions = Fusion.parse_csv(fusion_csv)
     ix = Indexer(ref.m_all_contigs, fusions, device)
     ix.make_index()
     try:
+        if chunk_bytes is not None:
+            mapper = FusionMapper(ix)
+            found, counters = _single_end_streamed(ix, mapper, read1_file, chunk_bytes)
+            kept, removed = mapper.filter_matches(found, deletion_threshold)
+            tail = {k: counters.pop(k) for k in ("retried_reads", "chunks")}
+            counters = {**counters, **removed, **tail}
+            if _keep is not None:
+                _keep.update(fusions=fusions, fusion_seq=list(ix.m_fusion_seq))
+            return FusionMapper.sort_matches(kept), counters
         b, text = FastqReader(read1_file).read_all_device(ix)
         if route == "device":
             found, extra = _single_end_device(ix, b, text)
@@ -149,13 +217,14 @@ def _single_end_device(ix: Indexer, b, text: bytes) -> Tuple[List[ReadMatch], di
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
-                           settings: Settings = None, route: str = "device") -> Tuple[List[FusionResult], dict]:
-    """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``: see
+                           settings: Settings = None, route: str = "device",
+                           chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
+    """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``: see
     ``scan_single_end_files``."""
     settings = settings or Settings()
     keep: dict = {}
     kept, counters = scan_single_end_files(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold, keep,
-                                           route=route)
+                                           route=route, chunk_bytes=chunk_bytes)
     results = cluster_matches(group_and_sort(kept, len(keep["fusions"])), keep["fusions"], keep["fusion_seq"], settings)
     counters["fusions"] = len(results)
     return results, counters

@@ -1,0 +1,112 @@
+// The names of the hit records of a scan (include/gf_hit_names.h), cut from the FASTQ text in HBM:
+//
+//   where each record's name line lies, and how long it is    gf_hn_k_lengths (a thread per record)
+//   where each name goes: an exclusive scan of the lengths    gf_hn_k_scan (one block, in place on the offsets)
+//   the names, back to back, in record order                  gf_hn_k_copy (a wavefront per name)
+//
+// The number of records is on the device (min(totals[0], hits_cap)), so every grid is sized by hits_cap and strides.
+// Deterministic: the one atomic counts the records without a name line.
+#pragma once
+
+#include "../../include/gf_hit_names.h"
+#include "gf_scan_common.h"
+
+// one side's FASTQ text and the newline index gf_fastq_index_device wrote for it
+struct GfHnText {
+  const uint8_t* text;
+  const int64_t* nl_pos;
+  int64_t n_bytes, n_newlines;
+};
+
+__device__ __forceinline__ int64_t gf_hn_records(const int64_t* __restrict__ scan_totals, int64_t hits_cap) {
+  const int64_t n = scan_totals[0];
+  return n < 0 ? 0 : (n < hits_cap ? n : hits_cap);
+}
+
+// ---- lengths: start[k] = where record k's name line starts in its text, off[k] = its length (scanned in place by
+// gf_hn_k_scan).  Line 4 i starts after newline 4 i - 1 and ends at newline 4 i, or with the text.
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_hn_k_lengths(
+    const gf_pair_hit* __restrict__ hits, const int64_t* __restrict__ scan_totals, int64_t hits_cap,
+    int64_t pair_id_base, GfHnText L, GfHnText R, int64_t* __restrict__ start, int64_t* __restrict__ off,
+    unsigned long long* __restrict__ n_missing) {
+  const int64_t n = gf_hn_records(scan_totals, hits_cap);
+  const int64_t step = (int64_t)gridDim.x * GF_SCAN_THREADS;
+  for (int64_t k = (int64_t)blockIdx.x * GF_SCAN_THREADS + threadIdx.x; k < n; k += step) {
+    const GfHnText& T = hits[k].source == 2 ? R : L;
+    const int64_t i = hits[k].pair_id - pair_id_base;
+    int64_t s = 0, len = 0;
+    // (i <= n_newlines / 4 keeps 4 i from overflowing on a damaged record)
+    if (T.text && i >= 0 && i <= T.n_newlines / 4) {
+      const int64_t line = 4 * i;
+      s = line == 0 ? 0 : T.nl_pos[line - 1] + 1;
+      int64_t e = line < T.n_newlines ? T.nl_pos[line] : T.n_bytes;
+      s = s < 0 ? 0 : (s > T.n_bytes ? T.n_bytes : s);  // (an index that is not this text's: stay inside the text)
+      e = e < s ? s : (e > T.n_bytes ? T.n_bytes : e);
+      len = e - s;
+    } else {
+      atomicAdd(n_missing, 1ull);
+    }
+    start[k] = s;
+    off[k] = len;
+  }
+}
+
+// ---- scan: off[0 .. n) from lengths to exclusive offsets, off[n] the total; totals [0] .. [2].  One block: thread t
+// takes a run of consecutive records, the runs' sums are scanned across the block, every record's offset is its run's
+// base plus its place in the run.
+__global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_hn_k_scan(
+    const int64_t* __restrict__ scan_totals, int64_t hits_cap, int64_t names_cap, int64_t* __restrict__ off,
+    int64_t* __restrict__ totals) {
+  __shared__ long long s_w[GF_SCAN_TOTALS_THREADS / 64];
+  const int64_t n = gf_hn_records(scan_totals, hits_cap);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t per = (n + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
+  const int64_t t0 = (int64_t)threadIdx.x * per < n ? (int64_t)threadIdx.x * per : n;
+  const int64_t t1 = t0 + per < n ? t0 + per : n;
+  long long mine = 0;
+  for (int64_t t = t0; t < t1; ++t) mine += off[t];
+  long long y = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long z = __shfl_up(y, o);
+    if (lane >= o) y += z;
+  }
+  if (lane == 63) s_w[wave] = y;
+  __syncthreads();
+  long long base = 0, total = 0;
+  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
+    if (w < wave) base += s_w[w];
+    total += s_w[w];
+  }
+  long long pos = base + y - mine;
+  for (int64_t t = t0; t < t1; ++t) {  // (in place: a thread reads and writes its own run only)
+    const long long len = off[t];
+    off[t] = pos;
+    pos += len;
+  }
+  if (threadIdx.x == 0) {
+    off[n] = total;
+    totals[0] = n;
+    totals[1] = total;
+    totals[2] = total > names_cap ? 1 : 0;  // ([3] was counted by gf_hn_k_lengths)
+  }
+}
+
+// ---- copy: name k by the 64 lanes of one wavefront (lane j: bytes j, j + 64, ..): names are tens of bytes and a
+// thread that copied its own would be alone in its wavefront with one round trip per byte.  A name that does not fit
+// names_cap is not written at all.
+__global__ __launch_bounds__(GF_SCAN_THREADS) void gf_hn_k_copy(
+    const gf_pair_hit* __restrict__ hits, const int64_t* __restrict__ scan_totals, int64_t hits_cap,
+    const uint8_t* __restrict__ l_text, const uint8_t* __restrict__ r_text, const int64_t* __restrict__ start,
+    const int64_t* __restrict__ off, uint8_t* __restrict__ names, int64_t names_cap) {
+  const int64_t n = gf_hn_records(scan_totals, hits_cap);
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * (GF_SCAN_THREADS / 64);
+  for (int64_t k = (int64_t)blockIdx.x * (GF_SCAN_THREADS / 64) + (threadIdx.x >> 6); k < n; k += waves) {
+    const int64_t o = off[k], len = off[k + 1] - o;
+    if (len <= 0 || o + len > names_cap) continue;
+    const uint8_t* __restrict__ src = (hits[k].source == 2 ? r_text : l_text) + start[k];
+#pragma unroll 1
+    for (int64_t j = lane; j < len; j += 64) names[o + j] = src[j];
+  }
+}
