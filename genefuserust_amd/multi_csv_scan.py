@@ -20,7 +20,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _lib
 from ._lib import GF_ERR_NO_DEVICE, GfError
-from .fusion_result import FusionResult, Settings, cluster_matches, group_and_sort, report_json
+from .fusion_result import FusionResult, Settings, report_json
 from .indexer import Indexer
 from .read_pair import PairScan, companion_scan, gene_reversed_device
 
@@ -178,64 +178,27 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
-def _pairs_one_csv(ix: Indexer, prepared: PreparedPairs, l, ltext, r, rtext, deletion_threshold: int):
-    """What scan.scan_pair_end_files does after its FASTQ cut, on the prepared pairs."""
-    from .fastq import record_lines
-    from .fusion_mapper import FusionMapper
-    from .read_pair import finish_pair_hits
-    mapper = FusionMapper(ix)
-    n, max_len = prepared.n, prepared.max_read_len
-    caps = dict(hits_cap=max(1024, n // 8), bytes_cap=max(1024, n // 8) * 2 * max_len)
-    rec, hb, hq, tot = scan_prepared_pairs_device(ix, prepared, **caps).download()
-    if tot["overflow"]:   # unusually many matches or retries: once more with room for everything
-        caps = dict(hits_cap=3 * n, bytes_cap=2 * int(l.bases.numel() + r.bases.numel()) + 64, retry_cap=3 * n)
-        rec, hb, hq, tot = scan_prepared_pairs_device(ix, prepared, **caps).download()
-    found = []
-    for i, m in finish_pair_hits(mapper, rec, hb, hq):
-        # a match on R2 (or its reverse complement) carries R2's name; anything else R1's
-        m.m_name = record_lines(r, rtext, i)[0] if m.m_source == "r2" else record_lines(l, ltext, i)[0]
-        if m.m_source == "merged":
-            m.m_name += b" merged_diff_%d" % m.m_merge_diff
-        found.append(m)
-    kept, removed = mapper.filter_matches(found, deletion_threshold)
-    counters = {"pairs": n, "matches_before_filtering": len(found), "merged_pairs": tot["merged_pairs"],
-                "retried_reads": tot["retried_reads"], **removed}
-    return FusionMapper.sort_matches(kept), counters
-
-
-def _single_one_csv(ix: Indexer, b, text, deletion_threshold: int):
-    """What scan.scan_single_end_files(route="device") does after its FASTQ cut."""
-    from .fusion_mapper import FusionMapper
-    from .scan import _single_end_device
-    found, extra = _single_end_device(ix, b, text)
-    kept, removed = FusionMapper(ix).filter_matches(found, deletion_threshold)
-    counters = {"reads": b.n_records, "matches_before_filtering": len(found), **removed, **extra}
-    return FusionMapper.sort_matches(kept), counters
-
-
 def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
                           time: str = "") -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
-    alone.  The FASTA is read once and the FASTQ cut once; with ``read2_file`` the pairs are prepared once.  Per CSV:
+    alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
+    ``read2_file`` the pairs are prepared once, and ``scan.pairs_found`` scans the prepared pairs.  Per CSV:
     parse it, build its index, scan, finish, filter, sort, cluster; the index is closed before the next one.  With
     ``json_file`` each entry's ``report_json`` goes to its ``report_names`` name — two entries with the same stem share
     a name and the later one overwrites the earlier, as in the reference."""
     from .fastq import FastqReader, FastqReaderPair
-    from .indexer import FastaReader, Fusion
+    from .fusion_mapper import FusionMapper
+    from .scan import finish_matches, open_index, pairs_found, read_contigs, report_matches, single_end_found
     settings = settings or Settings()
     csvs = read_csv_list(csv_list_file)
     names = report_names(json_file, csvs)
-    ref = FastaReader(ref_file, True)
-    ref.read_all()
+    contigs = read_contigs(ref_file)
     out: List[Tuple[str, List[FusionResult], dict]] = []
     reads = prepared = None
     for k, csv in enumerate(csvs):
-        fusions = Fusion.parse_csv(csv)
-        ix = Indexer(ref.m_all_contigs, fusions, device)
-        ix.make_index()
-        try:
+        with open_index(contigs, csv, device) as (ix, fusions):
             if reads is None:   # (the first index names the device the records go to)
                 if read2_file:
                     reads = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
@@ -244,15 +207,14 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                                     max(l.max_read_len(), r.max_read_len(), 1))
                 else:
                     reads = FastqReader(read1_file).read_all_device(ix)
+            mapper = FusionMapper(ix)
             if read2_file:
-                (l, ltext), (r, rtext) = reads
-                kept, counters = _pairs_one_csv(ix, prepared, l, ltext, r, rtext, settings.deletion_threshold)
+                produced = pairs_found(mapper, reads, prepared.max_read_len,
+                                       lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps))
             else:
-                kept, counters = _single_one_csv(ix, reads[0], reads[1], settings.deletion_threshold)
-            results = cluster_matches(group_and_sort(kept, len(fusions)), fusions, list(ix.m_fusion_seq), settings)
-            counters["fusions"] = len(results)
-        finally:
-            ix.close()
+                produced = single_end_found(ix, mapper, *reads)
+            kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:])
+            results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings)
         if names:
             with open(names[k], "w") as f:
                 f.write(report_json(results, command, version, time, settings))

@@ -133,6 +133,31 @@ def gene_reversed_device(indexer: Indexer, dev):
     return cached
 
 
+def pair_scan_outputs(dev, hits_cap: int, bytes_cap: int) -> PairScan:
+    """The outputs every pair scan writes, allocated on ``dev``: room for ``hits_cap`` records and ``bytes_cap`` bytes of
+    matched reads (at least one of each), the totals zeroed."""
+    import torch
+    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
+    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
+    return PairScan(hits, hb, hq, torch.zeros(8, dtype=torch.int64, device=dev))
+
+
+def scan_with_room(scan, first_caps: dict, room_caps: dict, queue_behind=None):
+    """``scan(**first_caps)`` downloaded, and when its totals say that something did not fit (unusually many matches or
+    retries) once more as ``scan(**room_caps)``: the caller's capacities with room for everything.  ``queue_behind(res)``
+    runs after each scan and before its download (the synchronisation): work for the device that follows the scan.
+    Returns (the ``PairScan``, what ``queue_behind`` gave or None, what ``PairScan.download`` gave); raises
+    ``GfError(GF_ERR_CAPACITY)`` when the second scan overflowed too."""
+    for caps in (first_caps, room_caps):
+        res = scan(**caps)
+        behind = None if queue_behind is None else queue_behind(res)
+        out = res.download()
+        if not out[3]["overflow"]:
+            return res, behind, out
+    raise _lib.GfError(_lib.GF_ERR_CAPACITY, "a scan with room for everything overflowed: %r with %r" % (out[3], room_caps))
+
+
 def companion_scan(check, fn, head, dev, ws_bytes: int, hits_cap: int, bytes_cap: int, stream) -> PairScan:
     """What the scans of libgfse.so and libgfmcsv.so share around their call: the outputs of a ``PairScan`` and the
     workspace are allocated on ``dev``, ``fn(*head, workspace, its size, hits, hits_cap, hit bases, hit quals,
@@ -140,17 +165,14 @@ def companion_scan(check, fn, head, dev, ws_bytes: int, hits_cap: int, bytes_cap
     current one)."""
     import torch
     st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
-    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    out = pair_scan_outputs(dev, hits_cap, bytes_cap)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    check(fn(*head, ws.data_ptr(), ws_bytes, hits.data_ptr(), hits_cap, hb.data_ptr(), hq.data_ptr(), bytes_cap,
-             totals.data_ptr(), st))
+    check(fn(*head, ws.data_ptr(), ws_bytes, out.hits.data_ptr(), hits_cap, out.bases.data_ptr(), out.quals.data_ptr(),
+             bytes_cap, out.totals.data_ptr(), st))
     # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
     if stream is not None:
         ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
-    return PairScan(hits, hb, hq, totals)
+    return out
 
 
 def scan_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_quals, r_off, max_read_len: int,
@@ -172,10 +194,7 @@ def scan_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_qual
     st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     hits_cap = max(1024, n // 16) if hits_cap is None else hits_cap
     bytes_cap = hits_cap * 2 * max(int(max_read_len), 1) if bytes_cap is None else bytes_cap
-    hits = torch.empty((max(hits_cap, 1), 64), dtype=torch.uint8, device=dev)
-    hb = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    hq = torch.empty(max(bytes_cap, 1), dtype=torch.uint8, device=dev)
-    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    out = pair_scan_outputs(dev, hits_cap, bytes_cap)
     assert (l_qual_off is None) == (r_qual_off is None)
     if l_qual_off is not None:
         assert l_qual_off.dtype == torch.int64 and r_qual_off.dtype == torch.int64
@@ -183,15 +202,15 @@ def scan_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_qual
         _lib.check(_lib.lib().gf_scan_pairs_text_device(
             indexer._handle(), l_bases.data_ptr(), l_quals.data_ptr(), l_qual_off.data_ptr(), l_off.data_ptr(), l_bases.numel(),
             r_bases.data_ptr(), r_quals.data_ptr(), r_qual_off.data_ptr(), r_off.data_ptr(), r_bases.numel(), n,
-            int(max_read_len), int(pair_id_base), int(retry_cap), hits.data_ptr(), hits_cap, hb.data_ptr(), hq.data_ptr(),
-            bytes_cap, totals.data_ptr(), st))
-        return PairScan(hits, hb, hq, totals)
-    _lib.check(_lib.lib().gf_scan_pairs_device(
-        indexer._handle(), l_bases.data_ptr(), l_quals.data_ptr(), l_off.data_ptr(), l_bases.numel(),
-        r_bases.data_ptr(), r_quals.data_ptr(), r_off.data_ptr(), r_bases.numel(), n, int(max_read_len),
-        int(pair_id_base), int(retry_cap), hits.data_ptr(), hits_cap, hb.data_ptr(), hq.data_ptr(), bytes_cap,
-        totals.data_ptr(), st))
-    return PairScan(hits, hb, hq, totals)
+            int(max_read_len), int(pair_id_base), int(retry_cap), out.hits.data_ptr(), hits_cap, out.bases.data_ptr(),
+            out.quals.data_ptr(), bytes_cap, out.totals.data_ptr(), st))
+    else:
+        _lib.check(_lib.lib().gf_scan_pairs_device(
+            indexer._handle(), l_bases.data_ptr(), l_quals.data_ptr(), l_off.data_ptr(), l_bases.numel(),
+            r_bases.data_ptr(), r_quals.data_ptr(), r_off.data_ptr(), r_bases.numel(), n, int(max_read_len),
+            int(pair_id_base), int(retry_cap), out.hits.data_ptr(), hits_cap, out.bases.data_ptr(), out.quals.data_ptr(),
+            bytes_cap, out.totals.data_ptr(), st))
+    return out
 
 
 def finish_pair_hits_device(indexer: Indexer, scan: "PairScan", stream=None):
@@ -254,12 +273,10 @@ def scan_pair_end(mapper: FusionMapper, pairs: Sequence[SequenceReadPair]) -> Li
     t = [torch.from_numpy(a).to(dev) for a in (lb, lq, lo, rb, rq, ro)]
     max_len = max(int(np.diff(lo).max()), int(np.diff(ro).max()), 1)
     n = len(pairs)
-    res = scan_pairs_device(ix, *t, max_len, hits_cap=3 * n, bytes_cap=int(lb.size + rb.size) * 2 + 64)
-    rec, hb, hq, tot = res.download()
-    if tot["overflow"] & 1:   # more reverse-complement retries than the default capacity: once more with room for all
-        res = scan_pairs_device(ix, *t, max_len, hits_cap=3 * n, bytes_cap=int(lb.size + rb.size) * 2 + 64, retry_cap=3 * n)
-        rec, hb, hq, tot = res.download()
-    assert not tot["overflow"], tot
+    caps = dict(hits_cap=3 * n, bytes_cap=int(lb.size + rb.size) * 2 + 64)
+    # (more reverse-complement retries than the default capacity: once more with room for all)
+    rec, hb, hq, _ = scan_with_room(lambda **c: scan_pairs_device(ix, *t, max_len, **c), caps,
+                                    dict(caps, retry_cap=3 * n))[2]
     out: List[List[ReadMatch]] = [[] for _ in pairs]
     for p, m in finish_pair_hits(mapper, rec, hb, hq):
         out[p].append(m)

@@ -27,7 +27,7 @@ import numpy as np
 from . import _lib
 from .fusion_mapper import FusionMapper, ReadMatch
 from .indexer import Indexer
-from .read_pair import finish_pair_hits, scan_pairs_device
+from .read_pair import finish_pair_hits, scan_pairs_device, scan_with_room
 
 CARRY_MAX = 1 << 20  # bytes kept in front of a chunk for the previous chunk's tail
 
@@ -263,13 +263,9 @@ def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_le
             def gather(res, **cap):
                 return hit_names_device(indexer, res, texts[0], batches[0], *(() if single else (texts[1], batches[1])),
                                         pair_id_base=done, **cap) if names else None
-            res = scan()
-            nm = gather(res)   # (queued behind the scan: the record count stays on the device)
-            out = res.download()
-            if out[3]["overflow"]:   # unusually many matches or retries: once more with room for everything
-                res = scan(**room)
-                nm = gather(res)
-                out = res.download()
+            # (first with the library's default capacities; the names are queued behind the scan: the record count
+            #  stays on the device)
+            res, nm, out = scan_with_room(scan, {}, room, gather)
             name_list = None
             if names:
                 _, need, over, _ = (int(x) for x in nm.totals.cpu())
