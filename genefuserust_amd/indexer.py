@@ -246,14 +246,19 @@ class Indexer:
     """Drop-in for ``struct Indexer``; the index lives in HBM."""
 
     def __init__(self, reference: Optional[Mapping[str, BytesLike]], fusions: Sequence[Fusion],
-                 device: int = -1):
-        # Indexer::with_loaded_ref (indexer.rs:100-112)
+                 device: int = -1, gene_slices: Optional[Sequence[Optional[BytesLike]]] = None):
+        # Indexer::with_loaded_ref (indexer.rs:100-112); gene_slices: the slices of `fusions` already cut out (what
+        # resolve_gene_slice gives per gene, ref_cut.cut_gene_slices), instead of a reference to cut them from
         self.m_reference = reference
         self.m_fusions = list(fusions)
         self._fusion_seq: Optional[List[str]] = []
         self._device = device
         self._h: Optional[C.c_void_p] = None
         self._gene_slices: Optional[List[Optional[bytes]]] = None
+        if gene_slices is not None:
+            if len(gene_slices) != len(self.m_fusions):
+                raise ValueError("%d gene slices for %d fusions" % (len(gene_slices), len(self.m_fusions)))
+            self._gene_slices = [None if s is None else _as_bytes(s) for s in gene_slices]
 
     with_loaded_ref = classmethod(lambda cls, reference, fusions, device=-1: cls(reference, fusions, device))
 
@@ -263,9 +268,7 @@ class Indexer:
         """Boundary form: gene slices already cut out (what gf_index_build takes)."""
         fus = [Fusion(Gene("g%d" % i, "", 0, 0, bool(reversed_flags[i]) if reversed_flags else False))
                for i in range(len(slices))]
-        ix = cls(None, fus, device)
-        ix._gene_slices = [None if s is None else _as_bytes(s) for s in slices]
-        return ix
+        return cls(None, fus, device, gene_slices=slices)
 
     def get_ref(self):
         return self.m_reference

@@ -180,25 +180,34 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
-                          time: str = "") -> List[Tuple[str, List[FusionResult], dict]]:
+                          time: str = "", ref_chunk_bytes: int = None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
     ``read2_file`` the pairs are prepared once, and ``scan.pairs_found`` scans the prepared pairs.  Per CSV:
     parse it, build its index, scan, finish, filter, sort, cluster; the index is closed before the next one.  With
     ``json_file`` each entry's ``report_json`` goes to its ``report_names`` name — two entries with the same stem share
-    a name and the later one overwrites the earlier, as in the reference."""
+    a name and the later one overwrites the earlier, as in the reference.  ``ref_chunk_bytes``: None keeps every
+    contig of the FASTA on the host for the whole run; with a value one streamed pass over the FASTA cuts the gene
+    slices of all CSVs on the device (``ref_cut.cut_gene_slices``), and the results are the same."""
     from .fastq import FastqReader, FastqReaderPair
     from .fusion_mapper import FusionMapper
-    from .scan import finish_matches, open_index, pairs_found, read_contigs, report_matches, single_end_found
+    from .indexer import Fusion
+    from .scan import (GeneSlices, finish_matches, open_index, pairs_found, read_contigs, report_matches,
+                       single_end_found)
     settings = settings or Settings()
     csvs = read_csv_list(csv_list_file)
     names = report_names(json_file, csvs)
-    contigs = read_contigs(ref_file)
+    if ref_chunk_bytes is None:
+        refs = [read_contigs(ref_file)] * len(csvs)
+    else:
+        from .ref_cut import cut_gene_slices
+        refs = [GeneSlices(s) for s in cut_gene_slices(ref_file, [Fusion.parse_csv(c) for c in csvs], ref_chunk_bytes,
+                                                       device)]
     out: List[Tuple[str, List[FusionResult], dict]] = []
     reads = prepared = None
     for k, csv in enumerate(csvs):
-        with open_index(contigs, csv, device) as (ix, fusions):
+        with open_index(refs[k], csv, device) as (ix, fusions):
             if reads is None:   # (the first index names the device the records go to)
                 if read2_file:
                     reads = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
@@ -224,21 +233,22 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
 def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
-                chunk_bytes: int = None):
+                chunk_bytes: int = None, ref_chunk_bytes: int = None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
     gives ``scan_multi_csv_report``'s list.  ``chunk_bytes`` streams the FASTQ files of the single-CSV scanners
     (``scan.scan_pair_end_files``); multi-CSV mode keeps its reads resident, as the reference does, and raises
-    ``ValueError`` for it."""
+    ``ValueError`` for it.  ``ref_chunk_bytes`` streams the reference FASTA in every mode (``scan.open_index``,
+    ``scan_multi_csv_report``)."""
     from . import scan
     if _rust_stem_ext(fusion_file)[2] == "csv":
         if read2_file:
             results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings,
-                                                          chunk_bytes=chunk_bytes)
+                                                          chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes)
         else:
             results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings,
-                                                            chunk_bytes=chunk_bytes)
+                                                            chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes)
         if json_file:
             with open(json_file, "w") as f:
                 f.write(report_json(results, command, version, time, settings))
@@ -246,4 +256,4 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     if chunk_bytes is not None:
         raise ValueError("chunk_bytes: multi-CSV mode scans resident reads once per CSV and does not stream them")
     return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
-                                 version, time)
+                                 version, time, ref_chunk_bytes)

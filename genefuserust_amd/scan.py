@@ -32,13 +32,27 @@ def read_contigs(ref_file: str) -> dict:
     return ref.m_all_contigs
 
 
+class GeneSlices(list):
+    """The gene slices of one fusion CSV, already cut out of the reference (``ref_cut.cut_gene_slices``): what
+    ``open_index`` takes in place of the contigs."""
+
+
 @contextmanager
-def open_index(ref, fusion_csv: str, device: int = -1):
-    """FASTA (a file name, or the contigs ``read_contigs`` gave) + fusion CSV -> (the open ``Indexer`` with its index
-    made, the parsed fusions); the index is closed on the way out."""
-    contigs = read_contigs(ref) if isinstance(ref, str) else ref
+def open_index(ref, fusion_csv: str, device: int = -1, ref_chunk_bytes: int = None):
+    """FASTA (a file name, the contigs ``read_contigs`` gave, or the ``GeneSlices`` of this CSV) + fusion CSV -> (the
+    open ``Indexer`` with its index made, the parsed fusions); the index is closed on the way out.
+
+    ``ref_chunk_bytes`` (with a file name): None reads the FASTA whole on the host (``read_contigs``).  With a value
+    the file is streamed in chunks of that many bytes of plain text and the gene slices are cut out on the device
+    (``ref_cut.cut_gene_slices``): the same index, and no contigs on the host (``Indexer.m_reference`` is None)."""
     fusions = Fusion.parse_csv(fusion_csv)
-    ix = Indexer(contigs, fusions, device)
+    if isinstance(ref, str) and ref_chunk_bytes is not None:
+        from .ref_cut import cut_gene_slices
+        ref = GeneSlices(cut_gene_slices(ref, [fusions], ref_chunk_bytes, device)[0])
+    if isinstance(ref, GeneSlices):
+        ix = Indexer(None, fusions, device, gene_slices=ref)
+    else:
+        ix = Indexer(read_contigs(ref) if isinstance(ref, str) else ref, fusions, device)
     ix.make_index()
     try:
         yield ix, fusions
@@ -161,9 +175,12 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int) -
 
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
-                      chunk_bytes):
+                      chunk_bytes, ref_chunk_bytes=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
-    with open_index(ref_file, fusion_csv, device) as (ix, fusions):
+    if remove_alignables and ref_chunk_bytes is not None:
+        raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
+                         "reference")
+    with open_index(ref_file, fusion_csv, device, ref_chunk_bytes) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
             produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes)
@@ -180,36 +197,42 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
 
 def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                         deletion_threshold: int = 50, remove_alignables: bool = False,
-                        chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
+                        chunk_bytes: int = None, ref_chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
     ``chunk_bytes``: None reads both files whole.  With a value they are streamed in chunks of that many bytes of
     plain text (scan_stream.scan_pair_source_stream: read, gunzipped and uploaded while the previous chunk is
     scanned, the names of the matched reads gathered on the device), so that neither the host nor the device ever
-    holds a file; the matches and counters are the same, and the counters add ``chunks``."""
+    holds a file; the matches and counters are the same, and the counters add ``chunks``.
+
+    ``ref_chunk_bytes``: None reads the reference FASTA whole on the host.  With a value it is streamed in chunks too
+    and the gene slices are cut out on the device (``open_index``); matches and counters are the same.
+    ``remove_alignables`` needs whole contigs and raises ``ValueError`` with it."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
-                             remove_alignables, chunk_bytes)[:2]
+                             remove_alignables, chunk_bytes, ref_chunk_bytes)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
-                         settings: Settings = None, chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
+                         settings: Settings = None, chunk_bytes: int = None,
+                         ref_chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` of fusion_result.py turn the list into
-    the reference's stdout block and JSON file.  ``chunk_bytes``: see ``scan_pair_end_files``."""
+    the reference's stdout block and JSON file.  ``chunk_bytes``, ``ref_chunk_bytes``: see ``scan_pair_end_files``."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
-                                             settings.deletion_threshold, False, chunk_bytes), settings)
+                                             settings.deletion_threshold, False, chunk_bytes, ref_chunk_bytes), settings)
 
 
-def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes):
+def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
+                        ref_chunk_bytes=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
     if chunk_bytes is not None and route != "device":
         raise ValueError("chunk_bytes streams the file through the device route; route=%r reads it whole" % (route,))
-    with open_index(ref_file, fusion_csv, device) as (ix, fusions):
+    with open_index(ref_file, fusion_csv, device, ref_chunk_bytes) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
             produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes)
@@ -223,7 +246,7 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
 
 def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                           deletion_threshold: int = 50, route: str = "device",
-                          chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
+                          chunk_bytes: int = None, ref_chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -234,15 +257,16 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
 
     ``chunk_bytes`` (device route only): None reads the file whole; with a value it is streamed in chunks of that many
     bytes of plain text (scan_stream.scan_single_text_stream), as in ``scan_pair_end_files``; the counters add
-    ``chunks``."""
-    return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes)[:2]
+    ``chunks``.  ``ref_chunk_bytes`` (either route): the reference FASTA in chunks, see ``scan_pair_end_files``."""
+    return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
+                               ref_chunk_bytes)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
-                           settings: Settings = None, route: str = "device",
-                           chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
-    """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``: see
-    ``scan_single_end_files``."""
+                           settings: Settings = None, route: str = "device", chunk_bytes: int = None,
+                           ref_chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
+    """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
+    ``ref_chunk_bytes``: see ``scan_single_end_files``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
-                                               route, chunk_bytes), settings)
+                                               route, chunk_bytes, ref_chunk_bytes), settings)

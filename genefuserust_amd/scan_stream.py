@@ -128,10 +128,12 @@ class _Side:
             self.eof = self.source.at_end()
         self.chunk_len[slot] = n
         if n:
-            # through the library's own hipMemcpyAsync: torch only treats memory of its own pinned allocator as
-            # pinned, and copies from anything else (gf_host_alloc memory included) synchronously
-            _lib.check(_lib.lib().gf_copy_from_host_device(self.h, ptr, self.bufs[slot].data_ptr() + CARRY_MAX, n,
-                                                           stream.cuda_stream))
+            self._copy(ptr, self.bufs[slot].data_ptr() + CARRY_MAX, n, stream.cuda_stream)
+
+    def _copy(self, ptr: int, dst: int, n: int, stream: int) -> None:
+        # through the library's own hipMemcpyAsync: torch only treats memory of its own pinned allocator as
+        # pinned, and copies from anything else (gf_host_alloc memory included) synchronously
+        _lib.check(_lib.lib().gf_copy_from_host_device(self.h, ptr, dst, n, stream))
 
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool):
