@@ -248,3 +248,55 @@ def load_companion(path: str, feature: str) -> C.CDLL:
             "%s not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). The %s has no CPU fallback." % (name, path, feature))
     return C.CDLL(path)
+
+
+def companion(path: str, feature: str, last_error: str, signatures: dict):
+    """``(lib, check)`` of a companion library: ``lib()`` loads it (once, ``load_companion``) and sets the ctypes
+    signatures ``{entry point: (restype, argtypes)}``; ``check(rc)`` raises ``GfError`` with what the library's
+    ``last_error`` entry point says when ``rc`` is negative."""
+    loaded = []
+
+    def lib() -> C.CDLL:
+        if not loaded:
+            L = load_companion(path, feature)
+            for name, (restype, argtypes) in signatures.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
+            loaded.append(L)
+        return loaded[0]
+
+    def check(rc: int) -> int:
+        if rc < 0:
+            raise GfError(rc, getattr(lib(), last_error)().decode("utf-8", "replace"))
+        return rc
+    return lib, check
+
+
+# ---- around a device call ---------------------------------------------------------------------------------------------
+
+def need_device_tensors(what: str, *tensors) -> None:
+    import torch
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GfError(GF_ERR_NO_DEVICE, "%s takes device tensors (there is no CPU fallback)" % what)
+
+
+def stream_handle(dev, stream=None) -> int:
+    """``stream`` (a raw handle), or the current stream of ``dev``."""
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+
+
+def for_stream(tensor, stream=None):
+    """``tensor``, allocated on the current stream, for a call queued on ``stream``: the caching allocator frees it on
+    the current stream, where later work runs after the call; an external stream has to be told of."""
+    import torch
+    if stream is not None:
+        tensor.record_stream(torch.cuda.ExternalStream(stream, device=tensor.device))
+    return tensor
+
+
+def workspace(nbytes: int, dev, stream=None):
+    """A workspace of ``nbytes`` (at least one) on ``dev`` for a call queued on ``stream``."""
+    import torch
+    return for_stream(torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), stream)

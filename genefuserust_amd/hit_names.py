@@ -15,38 +15,21 @@ import os
 from typing import List, NamedTuple, Optional
 
 from . import _lib
-from ._lib import GF_ERR_CAPACITY, GF_ERR_NO_DEVICE, GfError
+from ._lib import GF_ERR_CAPACITY, GfError
 from .indexer import Indexer
 from .read_pair import PairScan
 
 HN_LIB_PATH = os.path.join(_lib._HERE, "libgfnames.so")
 
-_hn = None
-
-
-def lib() -> C.CDLL:
-    """Load libgfnames.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names
-    another libgfmatch.so than the one libgfnames.so links against (two builds of the mapping in one process)."""
-    global _hn
-    if _hn is not None:
-        return _hn
-    L = _lib.load_companion(HN_LIB_PATH, "hit-name gather")
-    vp, i64 = C.c_void_p, C.c_int64
-    L.gf_hn_workspace_bytes.argtypes = [i64]
-    L.gf_hn_workspace_bytes.restype = i64
-    L.gf_hn_names_device.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp,
-                                     vp]
-    L.gf_hn_names_device.restype = C.c_int
-    L.gf_hn_last_error.argtypes = []
-    L.gf_hn_last_error.restype = C.c_char_p
-    _hn = L
-    return L
-
-
-def check(rc: int) -> int:
-    if rc < 0:
-        raise GfError(rc, lib().gf_hn_last_error().decode("utf-8", "replace"))
-    return rc
+_vp, _i64 = C.c_void_p, C.c_int64
+# libgfnames.so, loaded (once) after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
+# libgfmatch.so than the one libgfnames.so links against (two builds of the mapping in one process).
+lib, check = _lib.companion(HN_LIB_PATH, "hit-name gather", "gf_hn_last_error", {
+    "gf_hn_workspace_bytes": (_i64, [_i64]),
+    "gf_hn_names_device": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                     _vp, _i64, _vp, _vp, _vp]),
+    "gf_hn_last_error": (C.c_char_p, []),
+})
 
 
 class HitNames(NamedTuple):
@@ -77,9 +60,7 @@ def hit_names_device(indexer: Indexer, scan: PairScan, l_text, l_batch, r_text=N
     capacity; ``totals`` says when that was too small, and how much is needed)."""
     import torch
     tensors = [scan.hits, scan.totals, l_text, l_batch.nl_pos] + ([] if r_text is None else [r_text, r_batch.nl_pos])
-    for t in tensors:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise GfError(GF_ERR_NO_DEVICE, "hit_names_device takes device tensors (there is no CPU fallback)")
+    _lib.need_device_tensors("hit_names_device", *tensors)
     assert l_text.dtype == torch.uint8 and l_text.is_contiguous() and l_batch.nl_pos.dtype == torch.int64
     assert l_batch.nl_pos.is_contiguous() and l_batch.nl_pos.numel() >= l_batch.n_newlines
     if r_text is not None:
@@ -89,9 +70,8 @@ def hit_names_device(indexer: Indexer, scan: PairScan, l_text, l_batch, r_text=N
     dev = l_text.device
     hits_cap = int(scan.hits.shape[0])
     names_cap = 64 * hits_cap if names_cap is None else int(names_cap)
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     ws_bytes = int(L.gf_hn_workspace_bytes(hits_cap))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(ws_bytes, dev, stream)
     names = torch.empty(max(names_cap, 1), dtype=torch.uint8, device=dev)
     offsets = torch.empty(hits_cap + 1, dtype=torch.int64, device=dev)
     totals = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -100,8 +80,5 @@ def hit_names_device(indexer: Indexer, scan: PairScan, l_text, l_batch, r_text=N
     check(L.gf_hn_names_device(indexer._handle(), scan.hits.data_ptr(), scan.totals.data_ptr(), hits_cap,
                                int(pair_id_base), l_text.data_ptr(), l_text.numel(), l_batch.nl_pos.data_ptr(),
                                int(l_batch.n_newlines), *right, ws.data_ptr(), ws_bytes, names.data_ptr(), names_cap,
-                               offsets.data_ptr(), totals.data_ptr(), st))
-    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the call)
-    if stream is not None:
-        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+                               offsets.data_ptr(), totals.data_ptr(), _lib.stream_handle(dev, stream)))
     return HitNames(names, offsets, totals)

@@ -19,45 +19,24 @@ import os
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _lib
-from ._lib import GF_ERR_NO_DEVICE, GfError
 from .fusion_result import FusionResult, Settings, report_json
 from .indexer import Indexer
 from .read_pair import PairScan, companion_scan, gene_reversed_device
 
 MC_LIB_PATH = os.path.join(_lib._HERE, "libgfmcsv.so")
 
-_mc = None
-
-
-def lib() -> C.CDLL:
-    """Load libgfmcsv.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
-    libgfmatch.so than the one libgfmcsv.so links against (two builds of the mapping in one process)."""
-    global _mc
-    if _mc is not None:
-        return _mc
-    L = _lib.load_companion(MC_LIB_PATH, "multi-CSV scan")
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    L.gf_mc_prepared_bytes.argtypes = [i64, i64, i64, i32]
-    L.gf_mc_prepared_bytes.restype = i64
-    L.gf_mc_retry_capacity.argtypes = [i64]
-    L.gf_mc_retry_capacity.restype = i64
-    L.gf_mc_scan_workspace_bytes.argtypes = [i64, i32, i64]
-    L.gf_mc_scan_workspace_bytes.restype = i64
-    L.gf_mc_pairs_prepare_device.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, vp]
-    L.gf_mc_pairs_prepare_device.restype = C.c_int
-    L.gf_mc_pairs_scan_device.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, vp, i32, i64, i64, vp, i64,
-                                          vp, i64, vp, vp, i64, vp, vp]
-    L.gf_mc_pairs_scan_device.restype = C.c_int
-    L.gf_mc_last_error.argtypes = []
-    L.gf_mc_last_error.restype = C.c_char_p
-    _mc = L
-    return L
-
-
-def check(rc: int) -> int:
-    if rc < 0:
-        raise GfError(rc, lib().gf_mc_last_error().decode("utf-8", "replace"))
-    return rc
+_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+# libgfmcsv.so, loaded (once) after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
+# libgfmatch.so than the one libgfmcsv.so links against (two builds of the mapping in one process).
+lib, check = _lib.companion(MC_LIB_PATH, "multi-CSV scan", "gf_mc_last_error", {
+    "gf_mc_prepared_bytes": (_i64, [_i64, _i64, _i64, _i32]),
+    "gf_mc_retry_capacity": (_i64, [_i64]),
+    "gf_mc_scan_workspace_bytes": (_i64, [_i64, _i32, _i64]),
+    "gf_mc_pairs_prepare_device": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "gf_mc_pairs_scan_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32,
+                                          _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "gf_mc_last_error": (C.c_char_p, []),
+})
 
 
 class PreparedPairs(NamedTuple):
@@ -90,9 +69,7 @@ def prepare_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_q
     does not depend on the fusion CSV, once, asynchronously.  ``indexer`` only names the device: the result stays valid
     after it is closed.  Tensors as for ``read_pair.scan_pairs_device``."""
     import torch
-    for t in (l_bases, l_quals, l_off, r_bases, r_quals, r_off):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise GfError(GF_ERR_NO_DEVICE, "prepare_pairs_device takes device tensors (there is no CPU fallback)")
+    _lib.need_device_tensors("prepare_pairs_device", l_bases, l_quals, l_off, r_bases, r_quals, r_off)
     for t in (l_bases, l_quals, r_bases, r_quals):
         assert t.dtype == torch.uint8 and t.is_contiguous()
     n = l_off.numel() - 1
@@ -101,14 +78,12 @@ def prepare_pairs_device(indexer: Indexer, l_bases, l_quals, l_off, r_bases, r_q
     assert l_quals.numel() >= l_bases.numel() and r_quals.numel() >= r_bases.numel()
     L = lib()
     dev = l_bases.device
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     nbytes = int(L.gf_mc_prepared_bytes(n, l_bases.numel(), r_bases.numel(), int(max_read_len)))
-    buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    buf = _lib.workspace(nbytes, dev, stream)
     check(L.gf_mc_pairs_prepare_device(indexer._handle(), l_bases.data_ptr(), l_quals.data_ptr(), l_off.data_ptr(),
                                        l_bases.numel(), r_bases.data_ptr(), r_quals.data_ptr(), r_off.data_ptr(),
-                                       r_bases.numel(), n, int(max_read_len), buf.data_ptr(), nbytes, st))
-    if stream is not None:
-        buf.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+                                       r_bases.numel(), n, int(max_read_len), buf.data_ptr(), nbytes,
+                                       _lib.stream_handle(dev, stream)))
     return PreparedPairs(buf, l_bases, l_quals, l_off, r_bases, r_quals, r_off, n, int(max_read_len))
 
 

@@ -163,15 +163,10 @@ def companion_scan(check, fn, head, dev, ws_bytes: int, hits_cap: int, bytes_cap
     workspace are allocated on ``dev``, ``fn(*head, workspace, its size, hits, hits_cap, hit bases, hit quals,
     bytes_cap, totals, stream)`` is called through ``check``, and the workspace is tied to ``stream`` (None: the
     current one)."""
-    import torch
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     out = pair_scan_outputs(dev, hits_cap, bytes_cap)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(ws_bytes, dev, stream)
     check(fn(*head, ws.data_ptr(), ws_bytes, out.hits.data_ptr(), hits_cap, out.bases.data_ptr(), out.quals.data_ptr(),
-             bytes_cap, out.totals.data_ptr(), st))
-    # (the workspace is freed by the caching allocator on this stream: later work on the stream runs after the scan)
-    if stream is not None:
-        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+             bytes_cap, out.totals.data_ptr(), _lib.stream_handle(dev, stream)))
     return out
 
 

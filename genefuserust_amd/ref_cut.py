@@ -10,7 +10,8 @@ out the few Mbp it needs.  ``cut_gene_slices`` gives the same slices — exactly
     gf_rc_index_device (records, names, kept counts)  -->  one small read-back  -->  ``CutPlan`` (which ranges of which
     records are wanted)  -->  gf_rc_gather_device  -->  the wanted bytes, upper-cased, back to the host.
 
-``CutPlan`` is pure Python and needs no GPU.  libgfrefcut.so is a library of its own next to libgfmatch.so
+The chunk loop — staging blocks, upload thread, text buffers, carry — is ``chunk_stream.ChunkStream``, the one the streamed
+FASTQ scans run on.  ``CutPlan`` is pure Python and needs no GPU.  libgfrefcut.so is a library of its own next to libgfmatch.so
 (genefuserust_amd/scan_csrc/); it is loaded after ``_lib.lib()``, whose pinned allocator the staging blocks come from.
 No CPU fallback: without the libraries and a GPU every device call raises.
 """
@@ -19,52 +20,30 @@ from __future__ import annotations
 import bisect
 import ctypes as C
 import os
-import threading
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
-from ._lib import GF_ERR_CAPACITY, GF_ERR_NO_DEVICE, GfError
+from ._lib import GF_ERR_CAPACITY, GfError
+from .chunk_stream import CARRY_MAX, ChunkStream, checked_chunk_bytes, whole_read_sizes
 from .fastq import FastqByteStream
 from .indexer import Fusion
-from .scan_stream import CARRY_MAX, _Side
 
 RC_LIB_PATH = os.path.join(_lib._HERE, "libgfrefcut.so")
 
-_rc = None
-
-
-def lib() -> C.CDLL:
-    """Load libgfrefcut.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names
-    another libgfmatch.so than the one libgfrefcut.so links against."""
-    global _rc
-    if _rc is not None:
-        return _rc
-    L = _lib.load_companion(RC_LIB_PATH, "reference cut")
-    vp, i64 = C.c_void_p, C.c_int64
-    L.gf_rc_tile_bytes.argtypes = []
-    L.gf_rc_tile_bytes.restype = i64
-    L.gf_rc_tiles.argtypes = [i64]
-    L.gf_rc_tiles.restype = i64
-    L.gf_rc_workspace_bytes.argtypes = [i64]
-    L.gf_rc_workspace_bytes.restype = i64
-    L.gf_rc_index_device.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
-    L.gf_rc_index_device.restype = C.c_int
-    L.gf_rc_gather_device.argtypes = [vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-    L.gf_rc_gather_device.restype = C.c_int
-    L.gf_rc_copy_from_host_device.argtypes = [vp, vp, i64, vp]
-    L.gf_rc_copy_from_host_device.restype = C.c_int
-    L.gf_rc_last_error.argtypes = []
-    L.gf_rc_last_error.restype = C.c_char_p
-    _rc = L
-    return L
-
-
-def check(rc: int) -> int:
-    if rc < 0:
-        raise GfError(rc, lib().gf_rc_last_error().decode("utf-8", "replace"))
-    return rc
+_vp, _i64 = C.c_void_p, C.c_int64
+# libgfrefcut.so, loaded (once) after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
+# libgfmatch.so than the one libgfrefcut.so links against.
+lib, check = _lib.companion(RC_LIB_PATH, "reference cut", "gf_rc_last_error", {
+    "gf_rc_tile_bytes": (_i64, []),
+    "gf_rc_tiles": (_i64, [_i64]),
+    "gf_rc_workspace_bytes": (_i64, [_i64]),
+    "gf_rc_index_device": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "gf_rc_gather_device": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "gf_rc_copy_from_host_device": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "gf_rc_last_error": (C.c_char_p, []),
+})
 
 
 def tile_bytes() -> int:
@@ -122,8 +101,7 @@ class RefIndex(NamedTuple):
 
 def _device_text(text, what: str):
     import torch
-    if not isinstance(text, torch.Tensor) or not text.is_cuda:
-        raise GfError(GF_ERR_NO_DEVICE, "%s takes device tensors (there is no CPU fallback)" % what)
+    _lib.need_device_tensors(what, text)
     assert text.dtype == torch.uint8 and text.is_contiguous()
 
 
@@ -135,9 +113,8 @@ def ref_index_device(text, cap_records: int = 1024, names_cap: int = 1 << 16, st
     dev = text.device
     n = text.numel()
     cap_records, names_cap = int(cap_records), int(names_cap)
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     ws_bytes = int(L.gf_rc_workspace_bytes(n))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(ws_bytes, dev, stream)
     tile_kept = torch.empty(int(L.gf_rc_tiles(n)) + 1, dtype=torch.int64, device=dev)
     ix = RefIndex(torch.empty(8 + 5 * cap_records + 1 + (names_cap + 7) // 8, dtype=torch.int64, device=dev), tile_kept,
                   cap_records, names_cap)
@@ -145,9 +122,7 @@ def ref_index_device(text, cap_records: int = 1024, names_cap: int = 1 << 16, st
     check(L.gf_rc_index_device(text.data_ptr() if n else None, n, cap_records, ws.data_ptr(), ws_bytes,
                                gt_pos.data_ptr(), gt_rank.data_ptr(), name_end.data_ptr(), seq_rank.data_ptr(),
                                name_off.data_ptr(), names.data_ptr() if names_cap else None, names_cap,
-                               tile_kept.data_ptr(), totals.data_ptr(), st))
-    if stream is not None:
-        ws.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+                               tile_kept.data_ptr(), totals.data_ptr(), _lib.stream_handle(dev, stream)))
     return ix
 
 
@@ -160,17 +135,14 @@ def ref_gather_device(text, index: RefIndex, n_records: int, intervals, out_byte
     _device_text(text, "ref_gather_device")
     dev = text.device
     iv = np.ascontiguousarray(np.asarray(intervals, dtype=np.int64).reshape(-1, 4))
-    d_iv = torch.from_numpy(iv).to(dev)
+    d_iv = _lib.for_stream(torch.from_numpy(iv).to(dev), stream)
     if out is None:
         out = torch.empty(max(int(out_bytes), 1), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     n = text.numel()
     check(lib().gf_rc_gather_device(text.data_ptr() if n else None, n, index.part(1).data_ptr(),
                                     index.part(4).data_ptr(), int(n_records), index.tile_kept.data_ptr(),
                                     int(carried_kept), d_iv.data_ptr() if iv.shape[0] else None, iv.shape[0],
-                                    out.data_ptr(), int(out_bytes), st))
-    if stream is not None:
-        d_iv.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+                                    out.data_ptr(), int(out_bytes), _lib.stream_handle(dev, stream)))
     return out
 
 
@@ -336,16 +308,6 @@ class CutPass:
 
 # ---- the pass over the file ---------------------------------------------------------------------------------------
 
-class _RefSide(_Side):
-    """``scan_stream._Side`` without an index: the staging blocks cross the link by this library's own copy."""
-
-    def __init__(self, source, chunk_bytes: int, dev):
-        super().__init__(source, chunk_bytes, dev, None)
-
-    def _copy(self, ptr: int, dst: int, n: int, stream: int) -> None:
-        check(lib().gf_rc_copy_from_host_device(ptr, dst, n, stream))
-
-
 def _index_with_room(text, caps: dict) -> Tuple[RefIndex, ChunkRecords]:
     """``ref_index_device`` + its read-back, once more with the room the first call asked for when it was too small
     (``caps`` keeps what was needed for the chunks that follow)."""
@@ -372,78 +334,30 @@ def cut_gene_slices(ref_file: str, fusion_lists: Sequence[Sequence[Fusion]], chu
     its contig; ``GfError(GF_ERR_CAPACITY)`` for a record name of more than 1 MiB."""
     import torch
     ref_file = str(ref_file)
-    chunk_bytes = int(chunk_bytes)
-    if chunk_bytes < 1:
-        raise ValueError("chunk_bytes must be positive, not %r" % (chunk_bytes,))
+    chunk_bytes = checked_chunk_bytes(chunk_bytes)
     if os.path.isdir(ref_file):
         raise IsADirectoryError("There is a problem with the provided fasta file: '%s' is a directory NOT a file..."
                                 % ref_file)
     plan = CutPlan(fusion_lists)
     dev = torch.device("cuda", torch.cuda.current_device() if device < 0 else device)
-    copy_stream, proc = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-    free = [None, None]    # per slot: event after which the slot's buffer may be overwritten
-    threads: List[Optional[threading.Thread]] = [None, None]
-    errors: List[BaseException] = []
-    side = None
+    caps = dict(cap_records=1024, names_cap=1 << 16)
+    state = CutPass(plan)
 
-    def start_upload(slot: int) -> None:
-        """The slot's next chunk on a host thread of its own: reading the file (gunzip included) and queueing the copy
-        block that thread, not the one that launches the kernels of the chunk being processed."""
-        wait_for = free[slot]
+    def copy(ptr: int, dst: int, n: int, stream: int) -> None:
+        check(lib().gf_rc_copy_from_host_device(ptr, dst, n, stream))
 
-        def run():
-            try:
-                torch.cuda.set_device(dev)
-                if wait_for is not None:
-                    wait_for.synchronize()
-                side.upload(slot, chunk_bytes, copy_stream)
-                copy_stream.synchronize()
-            except BaseException as e:   # (handed to the consumer by wait_upload)
-                errors.append(e)
-        threads[slot] = threading.Thread(target=run)
-        threads[slot].start()
-
-    def wait_upload(slot: int) -> None:
-        threads[slot].join()
-        if errors:
-            raise errors[0]
+    def cut(texts, final):
+        text, = texts
+        if text.numel() == 0:   # (the first chunk: the chunk that holds a file's last byte is its last)
+            raise ValueError("empty fasta file: %s" % ref_file)
+        ix, rec = _index_with_room(text, caps)
+        nbytes = state.chunk(rec, text.numel(), final[0], lambda n, nbytes, rows, total, carried: (
+            ref_gather_device(text[:nbytes], ix, n, rows, total, carried).cpu().numpy().tobytes()))
+        if text.numel() - nbytes > CARRY_MAX:
+            raise GfError(GF_ERR_CAPACITY, "%s: a record name of more than %d bytes" % (ref_file, CARRY_MAX))
+        return [nbytes], [True], None
 
     with FastqByteStream(ref_file, ref_file.endswith(".gz")) as source:
-        try:
-            side = _RefSide(source, chunk_bytes, dev)
-            carry = torch.empty(0, dtype=torch.uint8, device=dev)
-            caps = dict(cap_records=1024, names_cap=1 << 16)
-            state = CutPass(plan)
-            slot = 0
-            start_upload(0)
-            while True:
-                wait_upload(slot)               # this chunk's text is on the device
-                if free[0] is None and side.chunk_len[0] == 0:
-                    raise ValueError("empty fasta file: %s" % ref_file)
-                final = side.done()             # the file's last byte is in this chunk
-                if not final:
-                    start_upload(slot ^ 1)      # the next chunk is read and crosses the link while this one is cut
-                with torch.cuda.stream(proc):
-                    buf, n0 = side.bufs[slot], carry.numel()
-                    if n0:
-                        buf[CARRY_MAX - n0:CARRY_MAX].copy_(carry)
-                    text = buf[CARRY_MAX - n0:CARRY_MAX + side.chunk_len[slot]]
-                    ix, rec = _index_with_room(text, caps)
-                    nbytes = state.chunk(rec, text.numel(), final, lambda n, nbytes, rows, total, carried: (
-                        ref_gather_device(text[:nbytes], ix, n, rows, total, carried).cpu().numpy().tobytes()))
-                    if text.numel() - nbytes > CARRY_MAX:
-                        raise GfError(GF_ERR_CAPACITY, "%s: a record name of more than %d bytes" % (ref_file, CARRY_MAX))
-                    carry = text[nbytes:].clone()
-                    free[slot] = torch.cuda.Event()
-                    free[slot].record(proc)
-                if final:
-                    break
-                slot ^= 1
-        finally:
-            for th in threads:
-                if th is not None:
-                    th.join()
-            torch.cuda.synchronize(dev)   # (no copy in flight out of the staging blocks)
-            if side is not None:
-                side.close()
+        for _ in ChunkStream([source], chunk_bytes, dev, copy, whole_read_sizes).run(cut):
+            pass
     return plan.finish()

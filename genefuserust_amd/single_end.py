@@ -13,40 +13,22 @@ import os
 from typing import Optional
 
 from . import _lib
-from ._lib import GF_ERR_NO_DEVICE, GF_ERR_READ_TOO_LONG, GfError
+from ._lib import GF_ERR_READ_TOO_LONG, GfError
 from .indexer import Indexer
 from .read_pair import PairScan, companion_scan, gene_reversed_device
 
 SE_LIB_PATH = os.path.join(_lib._HERE, "libgfse.so")
 
-_se = None
-
-
-def lib() -> C.CDLL:
-    """Load libgfse.so (once), after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
-    libgfmatch.so than the one libgfse.so links against (two builds of the mapping in one process)."""
-    global _se
-    if _se is not None:
-        return _se
-    L = _lib.load_companion(SE_LIB_PATH, "single-end scan")
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    L.gf_se_retry_capacity.argtypes = [i64]
-    L.gf_se_retry_capacity.restype = i64
-    L.gf_se_workspace_bytes.argtypes = [i64, i32, i64]
-    L.gf_se_workspace_bytes.restype = i64
-    L.gf_se_scan_device.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, i32, i64, i64, vp, i64, vp, i64, vp, vp, i64, vp,
-                                    vp]
-    L.gf_se_scan_device.restype = C.c_int
-    L.gf_se_last_error.argtypes = []
-    L.gf_se_last_error.restype = C.c_char_p
-    _se = L
-    return L
-
-
-def check(rc: int) -> int:
-    if rc < 0:
-        raise GfError(rc, lib().gf_se_last_error().decode("utf-8", "replace"))
-    return rc
+_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+# libgfse.so, loaded (once) after libgfmatch.so.  Raises if it has not been built, or if GFMATCH_LIB names another
+# libgfmatch.so than the one libgfse.so links against (two builds of the mapping in one process).
+lib, check = _lib.companion(SE_LIB_PATH, "single-end scan", "gf_se_last_error", {
+    "gf_se_retry_capacity": (_i64, [_i64]),
+    "gf_se_workspace_bytes": (_i64, [_i64, _i32, _i64]),
+    "gf_se_scan_device": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _i64,
+                                    _vp, _vp, _i64, _vp, _vp]),
+    "gf_se_last_error": (C.c_char_p, []),
+})
 
 
 def scan_single_device(indexer: Indexer, bases, quals, offsets, max_read_len: int, read_id_base: int = 0,
@@ -60,9 +42,7 @@ def scan_single_device(indexer: Indexer, bases, quals, offsets, max_read_len: in
     ``check_lengths``: wait for the totals and raise ``GfError(GF_ERR_READ_TOO_LONG)`` when a read is longer than
     ``max_read_len`` (totals[5]); False leaves the call fully asynchronous and the check to the caller."""
     import torch
-    for t in (bases, quals, offsets):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise GfError(GF_ERR_NO_DEVICE, "scan_single_device takes device tensors (there is no CPU fallback)")
+    _lib.need_device_tensors("scan_single_device", bases, quals, offsets)
     assert bases.dtype == torch.uint8 and quals.dtype == torch.uint8 and offsets.dtype == torch.int64
     assert quals.numel() >= bases.numel() and offsets.is_contiguous() and bases.is_contiguous() and quals.is_contiguous()
     L = lib()

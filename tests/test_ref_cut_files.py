@@ -198,3 +198,20 @@ def test_streamed_cut_holds_chunks_not_the_file(gpu_device, tmp_path):
     assert got == want and len(want[0]) >= 32 and all(len(s) == 3000 for s in want[0])
     assert long_ - short < c
     assert cut_peak < size
+
+
+@pytest.mark.gpu
+def test_a_truncated_gz_raises_what_the_host_reader_raises(gpu_device, tmp_path):
+    """The inflating upload thread fails in the middle of the file: the cut raises what the host reader raises on that
+    file, and the next cut is the mirror's."""
+    from genefuserust_amd.ref_cut import cut_gene_slices
+    lists = [_fusions(EDGE_GENES)]
+    bad, good = tmp_path / "cut_short.fa.gz", tmp_path / "whole.fa.gz"
+    bad.write_bytes(gzip.compress(EDGE_FASTA)[:-20])
+    good.write_bytes(gzip.compress(EDGE_FASTA))
+    with pytest.raises(Exception) as want:
+        FastaReader(str(bad), True).read_all()
+    with pytest.raises(Exception) as e:
+        cut_gene_slices(str(bad), lists, 64)
+    assert type(e.value) is type(want.value) and not isinstance(e.value, AssertionError)
+    assert cut_gene_slices(str(good), lists, 64) == _mirror(good, lists)

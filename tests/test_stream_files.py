@@ -419,3 +419,82 @@ def test_streamed_scan_holds_chunks_not_files(gpu_device, tmp_path, layout):
     assert _texts(res4) == _texts(resw)
     assert long_ - short < c
     assert long_ < whole
+
+
+# ---- 5. a byte source that fails ----------------------------------------------------------------------------------------
+
+class _Source:
+    """A byte source over a text in memory that does not lend its bytes (they go through the staging blocks);
+    ``fail_on``: the number of the ``readinto`` call that raises."""
+    name = "<test source>"
+
+    def __init__(self, text: bytes, fail_on: int = 0):
+        self.text, self.pos, self.calls, self.fail_on = text, 0, 0, fail_on
+
+    def readinto(self, mv) -> int:
+        self.calls += 1
+        if self.calls == self.fail_on:
+            raise OSError("boom")
+        n = min(len(mv), len(self.text) - self.pos)
+        mv[:n] = self.text[self.pos:self.pos + n]
+        self.pos += n
+        return n
+
+
+def _same_records(chunks, want):
+    """The records of a stream's chunks against a one-shot scan's download, the reads with them."""
+    rec = np.concatenate([t[0] for t in chunks])
+    assert rec.shape[0] == want[0].shape[0] == want[3]["hits"] > 0 and want[3]["overflow"] == 0   # (not vacuous)
+    for f in ("pair_id", "source", "flags", "read_len", "merge_diff"):
+        assert (rec[f] == want[0][f]).all(), f
+    assert rec["m"].tobytes() == want[0]["m"].tobytes()
+    k = 0
+    for t in chunks:
+        for h in t[0]:
+            o, ln, wo = int(h["seq_offset"]), int(h["read_len"]), int(want[0][k]["seq_offset"])
+            assert t[1][o:o + ln] == want[1][wo:wo + ln] and t[2][o:o + ln] == want[2][wo:wo + ln]
+            k += 1
+
+
+@pytest.mark.gpu
+def test_a_single_end_source_that_raises_reaches_the_consumer(gpu_device):
+    """The second ``readinto`` of the source raises on an upload thread: the iterator raises it, and the next scan on
+    the same index is the one-shot scan's."""
+    from genefuserust_amd.fastq import fastq_cut_device
+    from genefuserust_amd.scan_stream import scan_single_text_stream
+    from genefuserust_amd.single_end import scan_single_device
+    ix, genes = _golden_index()
+    pairs = _make_pairs(np.random.default_rng(8), genes, 300)
+    text = b"".join(b"@read%d\n%s\n+\n%s\n" % (k, p[0], p[1]) for k, p in enumerate(pairs))
+    assert len(text) > 10 * 4096
+    with pytest.raises(OSError, match="boom"):
+        list(scan_single_text_stream(ix, _Source(text, fail_on=2), chunk_bytes=4096, max_read_len=150))
+    got = list(scan_single_text_stream(ix, _Source(text), chunk_bytes=4096, max_read_len=150))
+    assert sum(t[4]["reads"] for t in got) == 300 and len(got) >= 10
+    b = fastq_cut_device(ix, _device_text(text))
+    want = scan_single_device(ix, b.bases, b.quals, b.offsets, 150, hits_cap=300, bytes_cap=len(text), retry_cap=300)
+    _same_records(got, want.download())
+    assert [n for t in got for n in t[3]] == [b"@read%d" % int(i) for t in got for i in t[0]["pair_id"]]
+    ix.close()
+
+
+@pytest.mark.gpu
+def test_a_second_file_that_raises_reaches_the_consumer(gpu_device):
+    """The same with pairs in which only R2's source raises: on the reader thread of the further side."""
+    from genefuserust_amd.fastq import fastq_cut_device
+    from genefuserust_amd.read_pair import scan_pairs_device
+    from genefuserust_amd.scan_stream import scan_pair_source_stream
+    ix, genes = _golden_index()
+    pairs = _make_pairs(np.random.default_rng(9), genes, 300)
+    t1 = b"".join(b"@pair%d/1\n%s\n+\n%s\n" % (k, p[0], p[1]) for k, p in enumerate(pairs))
+    t2 = b"".join(b"@pair%d/2\n%s\n+\n%s\n" % (k, p[2], p[3]) for k, p in enumerate(pairs))
+    assert len(t2) > 10 * 4096
+    with pytest.raises(OSError, match="boom"):
+        list(scan_pair_source_stream(ix, _Source(t1), _Source(t2, fail_on=2), chunk_bytes=4096, max_read_len=150))
+    got = list(scan_pair_source_stream(ix, _Source(t1), _Source(t2), chunk_bytes=4096, max_read_len=150))
+    assert sum(t[4]["pairs"] for t in got) == 300 and len(got) >= 10
+    b1, b2 = fastq_cut_device(ix, _device_text(t1)), fastq_cut_device(ix, _device_text(t2))
+    want = scan_pairs_device(ix, b1.bases, b1.quals, b1.offsets, b2.bases, b2.quals, b2.offsets, 150, hits_cap=900,
+                             bytes_cap=2 * (len(t1) + len(t2)), retry_cap=900)
+    _same_records(got, want.download())
+    ix.close()
