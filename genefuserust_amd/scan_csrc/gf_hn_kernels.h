@@ -51,39 +51,13 @@ __global__ __launch_bounds__(GF_SCAN_THREADS) void gf_hn_k_lengths(
   }
 }
 
-// ---- scan: off[0 .. n) from lengths to exclusive offsets, off[n] the total; totals [0] .. [2].  One block: thread t
-// takes a run of consecutive records, the runs' sums are scanned across the block, every record's offset is its run's
-// base plus its place in the run.
+// ---- scan: off[0 .. n) from lengths to exclusive offsets, off[n] the total; totals [0] .. [2].  One block, in place
+// (gf_scan_totals_block).
 __global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_hn_k_scan(
     const int64_t* __restrict__ scan_totals, int64_t hits_cap, int64_t names_cap, int64_t* __restrict__ off,
     int64_t* __restrict__ totals) {
-  __shared__ long long s_w[GF_SCAN_TOTALS_THREADS / 64];
   const int64_t n = gf_hn_records(scan_totals, hits_cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t per = (n + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
-  const int64_t t0 = (int64_t)threadIdx.x * per < n ? (int64_t)threadIdx.x * per : n;
-  const int64_t t1 = t0 + per < n ? t0 + per : n;
-  long long mine = 0;
-  for (int64_t t = t0; t < t1; ++t) mine += off[t];
-  long long y = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long z = __shfl_up(y, o);
-    if (lane >= o) y += z;
-  }
-  if (lane == 63) s_w[wave] = y;
-  __syncthreads();
-  long long base = 0, total = 0;
-  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
-    if (w < wave) base += s_w[w];
-    total += s_w[w];
-  }
-  long long pos = base + y - mine;
-  for (int64_t t = t0; t < t1; ++t) {  // (in place: a thread reads and writes its own run only)
-    const long long len = off[t];
-    off[t] = pos;
-    pos += len;
-  }
+  const long long total = gf_scan_totals_block(off, off, n);
   if (threadIdx.x == 0) {
     off[n] = total;
     totals[0] = n;

@@ -79,41 +79,15 @@ __global__ __launch_bounds__(GF_RC_THREADS) void gf_rc_k_count(GfRcText T, uint3
 }
 
 // ---- scan: the tiles' counts to exclusive offsets (tile_gt_off[0 .. ntiles), tile_kept[0 .. ntiles]) and the totals.
-// One block: thread t takes a run of consecutive tiles, the runs' sums are scanned across the block.
+// One block, both sequences in one pass (gf_scan_totals_block).
 __global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_rc_k_scan(
     const uint32_t* __restrict__ tile_gt, const uint32_t* __restrict__ tile_keep, int64_t ntiles, int64_t cap_records,
     int64_t* __restrict__ tile_gt_off, int64_t* __restrict__ tile_kept, int64_t* __restrict__ totals) {
-  __shared__ long long s_g[GF_SCAN_TOTALS_THREADS / 64], s_k[GF_SCAN_TOTALS_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t per = (ntiles + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
-  const int64_t t0 = (int64_t)threadIdx.x * per < ntiles ? (int64_t)threadIdx.x * per : ntiles;
-  const int64_t t1 = t0 + per < ntiles ? t0 + per : ntiles;
-  long long mg = 0, mk = 0;
-  for (int64_t t = t0; t < t1; ++t) {
-    mg += tile_gt[t];
-    mk += tile_keep[t];
-  }
-  long long yg = mg, yk = mk;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long zg = __shfl_up(yg, o), zk = __shfl_up(yk, o);
-    if (lane >= o) { yg += zg; yk += zk; }
-  }
-  if (lane == 63) { s_g[wave] = yg; s_k[wave] = yk; }
-  __syncthreads();
-  long long bg = 0, bk = 0, tg = 0, tk = 0;
-  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
-    if (w < wave) { bg += s_g[w]; bk += s_k[w]; }
-    tg += s_g[w];
-    tk += s_k[w];
-  }
-  long long pg = bg + yg - mg, pk = bk + yk - mk;
-  for (int64_t t = t0; t < t1; ++t) {
-    tile_gt_off[t] = pg;
-    tile_kept[t] = pk;
-    pg += tile_gt[t];
-    pk += tile_keep[t];
-  }
+  const uint32_t* const in[2] = {tile_gt, tile_keep};
+  int64_t* const out[2] = {tile_gt_off, tile_kept};
+  long long total[2];
+  gf_scan_totals_block(in, out, ntiles, total);
+  const long long tg = total[0], tk = total[1];
   if (threadIdx.x == 0) {
     tile_kept[ntiles] = tk;
     totals[0] = tg;
@@ -196,33 +170,8 @@ __global__ __launch_bounds__(GF_RC_THREADS) void gf_rc_k_names(GfRcText T, const
 __global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_rc_k_name_scan(int64_t cap_records, int64_t names_cap,
                                                                             int64_t* __restrict__ off,
                                                                             int64_t* __restrict__ totals) {
-  __shared__ long long s_w[GF_SCAN_TOTALS_THREADS / 64];
   const int64_t n = gf_rc_known(totals, cap_records);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t per = (n + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
-  const int64_t t0 = (int64_t)threadIdx.x * per < n ? (int64_t)threadIdx.x * per : n;
-  const int64_t t1 = t0 + per < n ? t0 + per : n;
-  long long mine = 0;
-  for (int64_t t = t0; t < t1; ++t) mine += off[t];
-  long long y = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long z = __shfl_up(y, o);
-    if (lane >= o) y += z;
-  }
-  if (lane == 63) s_w[wave] = y;
-  __syncthreads();
-  long long base = 0, total = 0;
-  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
-    if (w < wave) base += s_w[w];
-    total += s_w[w];
-  }
-  long long pos = base + y - mine;
-  for (int64_t t = t0; t < t1; ++t) {  // (in place: a thread reads and writes its own run only)
-    const long long len = off[t];
-    off[t] = pos;
-    pos += len;
-  }
+  const long long total = gf_scan_totals_block(off, off, n);
   if (threadIdx.x == 0) {
     off[n] = total;
     totals[4] = total;

@@ -1,7 +1,8 @@
 // What the scans built on libgfmatch.so's public ABI share on the device (libgfse.so: gf_se_kernels.h, libgfmcsv.so:
 // gf_mc_kernels.h): the status of a mapped read, the direction rule, the reverse complement, the block-wide scan, the
-// wavefront's copy of a read and the retry slots' tail.  Inlined device functions and plain structs only, no kernel:
-// every kernel keeps its library's name (gf_se_k_*, gf_mc_k_*), so that a profile tells the libraries apart.
+// wavefront's copy of a read and the retry slots' tail; and, with libgfnames.so and libgfrefcut.so too, the one-block
+// scan of the totals.  Inlined device functions and plain structs only, no kernel: every kernel keeps its library's
+// name (gf_se_k_*, gf_mc_k_*, ..), so that a profile tells the libraries apart.
 //
 // The direction rule and the complement are restated from csrc/gf_pair_kernels.h (gf_dev_required_direction,
 // gf_complement_base), which these libraries do not include: a second copy of that header's kernels under the same
@@ -75,8 +76,67 @@ __device__ __forceinline__ void gf_scan_block_scan2(int a, long long b, int* s_a
   __syncthreads();  // (s_a / s_b are reused by the next scan of the block)
 }
 
-// One job of gf_se_k_scan / gf_mc_k_scan, the exclusive scan of per-tile totals by one block.  The kernels' bodies are
-// not shared: inlined from here the same source is reassociated differently and takes 60 VGPRs instead of 52.
+// The whole body of the one-block scans (gf_se_k_scan, gf_mc_k_scan, gf_hn_k_scan, gf_rc_k_scan, gf_rc_k_name_scan):
+// the exclusive scan of S sequences of n elements, in one pass, by one block of GF_SCAN_TOTALS_THREADS threads.
+// Thread t takes a run of `per` consecutive elements (the threads past the last run take none), the runs' sums are
+// scanned across the block, and every element's offset is its run's base plus its place in the run.  total[s]: the sum
+// of sequence s, in every thread.  out[s] may be in[s] (a scan in place): an element is read before its offset is
+// stored, a thread reads and writes its own run only, and no pointer here is __restrict__.
+template <int S, typename In>
+__device__ __forceinline__ void gf_scan_totals_block(In* const (&in)[S], int64_t* const (&out)[S], int64_t n,
+                                                     long long (&total)[S]) {
+  __shared__ long long s_w[S][GF_SCAN_TOTALS_THREADS / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t per = (n + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
+  const int64_t t0 = (int64_t)threadIdx.x * per < n ? (int64_t)threadIdx.x * per : n;
+  const int64_t t1 = t0 + per < n ? t0 + per : n;
+  long long mine[S] = {}, y[S], pos[S];
+  for (int64_t t = t0; t < t1; ++t) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) mine[s] += in[s][t];
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    y[s] = mine[s];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long z = __shfl_up(y[s], o);
+      if (lane >= o) y[s] += z;
+    }
+    if (lane == 63) s_w[s][wave] = y[s];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    long long base = 0;
+    total[s] = 0;
+    for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
+      if (w < wave) base += s_w[s][w];
+      total[s] += s_w[s][w];
+    }
+    pos[s] = base + y[s] - mine[s];
+  }
+  for (int64_t t = t0; t < t1; ++t) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const long long v = in[s][t];
+      out[s][t] = pos[s];
+      pos[s] += v;
+    }
+  }
+}
+
+// ... of one sequence: returns its sum
+template <typename In>
+__device__ __forceinline__ long long gf_scan_totals_block(In* in, int64_t* out, int64_t n) {
+  In* const i1[1] = {in};
+  int64_t* const o1[1] = {out};
+  long long total[1];
+  gf_scan_totals_block(i1, o1, n, total);
+  return total[0];
+}
+
+// One job of gf_se_k_scan / gf_mc_k_scan, the exclusive scan of per-tile totals by one block.
 struct GfScanJob {
   const uint32_t* tile_counts;
   int64_t* tile_offsets;

@@ -74,38 +74,13 @@ __global__ __launch_bounds__(GF_SCAN_THREADS) void gf_se_k_classify(
 }
 
 // ---- exclusive scan of per-tile totals: block b scans job b (the scans come in pairs: reads and bytes) ----
-// Thread t takes a run of consecutive totals, the runs' sums are scanned across the block, every total's offset is
-// its run's base plus its place in the run.  A batch of 20 M reads has 4 883 tiles: five totals per thread.
+// (gf_scan_totals_block.)  A batch of 20 M reads has 4 883 tiles: five totals per thread.
 struct GfSeScanJobs { GfScanJob j[2]; };
 
 __global__ __launch_bounds__(GF_SCAN_TOTALS_THREADS) void gf_se_k_scan(GfSeScanJobs jobs, int64_t ntiles) {
-  const uint32_t* __restrict__ cnt = jobs.j[blockIdx.x].tile_counts;
-  int64_t* __restrict__ off = jobs.j[blockIdx.x].tile_offsets;
-  __shared__ long long s_w[GF_SCAN_TOTALS_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t per = (ntiles + GF_SCAN_TOTALS_THREADS - 1) / GF_SCAN_TOTALS_THREADS;
-  const int64_t t0 = (int64_t)threadIdx.x * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
-  long long mine = 0;
-  for (int64_t t = t0; t < t1; ++t) mine += cnt[t];
-  long long y = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long z = __shfl_up(y, o);
-    if (lane >= o) y += z;
-  }
-  if (lane == 63) s_w[wave] = y;
-  __syncthreads();
-  long long base = 0, total = 0;
-  for (int w = 0; w < GF_SCAN_TOTALS_THREADS / 64; ++w) {
-    if (w < wave) base += s_w[w];
-    total += s_w[w];
-  }
-  long long pos = base + y - mine;
-  for (int64_t t = t0; t < t1; ++t) {
-    off[t] = pos;
-    pos += cnt[t];
-  }
-  if (threadIdx.x == 0) *jobs.j[blockIdx.x].d_total = total;
+  const GfScanJob& j = jobs.j[blockIdx.x];
+  const long long total = gf_scan_totals_block(j.tile_counts, j.tile_offsets, ntiles);
+  if (threadIdx.x == 0) *j.d_total = total;
 }
 
 // ---- retry_write: the reverse complements of the retried reads, back to back, in read order ----

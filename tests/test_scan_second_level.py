@@ -1,6 +1,7 @@
 """The second level of the companion libraries' two-level scans: gf_se_k_scan (libgfse.so), gf_mc_k_scan (libgfmcsv.so),
-gf_hn_k_scan (libgfnames.so), gf_rc_k_scan and gf_rc_k_name_scan (libgfrefcut.so).  One block of SCAN_THREADS threads
-scans the per-tile totals; thread t takes a run of ``per = ceil(n / SCAN_THREADS)`` consecutive totals.  The other
+gf_hn_k_scan (libgfnames.so), gf_rc_k_scan and gf_rc_k_name_scan (libgfrefcut.so).  The five kernels share one body
+(gf_scan_totals_block, gf_scan_common.h) and keep their own tails.  One block of SCAN_THREADS threads scans the per-tile
+totals; thread t takes a run of ``per = ceil(n / SCAN_THREADS)`` consecutive totals.  The other
 modules stay at ``per = 1`` and inside one or two wavefronts of that block; here every batch is the smallest that
 crosses a threshold — the second wavefront, runs of two and more totals, a shorter last run, trailing threads without a
 run, a second iteration of the names' grid-stride loops — and nearly every element is a filler that gives nothing, so
@@ -8,7 +9,7 @@ the expected output is known by construction from a few dozen planted elements w
 
 Every size below is a formula over the constants named first, and a test without a GPU holds those constants to the
 ``#define``s of the sources: a later change of a tile size fails here and does not quietly bring the coverage back to
-``per = 1``."""
+``per = 1``.  The same test holds the split into runs to one place, the shared body, and each kernel to its header."""
 import os
 import re
 from typing import NamedTuple, Tuple
@@ -94,11 +95,16 @@ def test_sizes_are_the_sources_defines():
     src = open(os.path.join(SCAN_CSRC, "gf_hit_names.hip")).read()
     m = re.search(r"g_len\s*=.*?\(hits_cap \+ GF_SCAN_THREADS - 1\) / GF_SCAN_THREADS,\s*(\d+)\)", src)
     assert m and int(m.group(1)) == HN_GRID_BLOCKS
-    # every scan kernel splits its totals the same way
-    for header, kernels in (("gf_se_kernels.h", 1), ("gf_mc_kernels.h", 1), ("gf_hn_kernels.h", 1), ("gf_rc_kernels.h", 2)):
+    # the split of the totals is written once, in the shared body, and every scan kernel is still its library's own
+    split = r"per = \((?:ntiles|n) \+ GF_SCAN_TOTALS_THREADS - 1\) / GF_SCAN_TOTALS_THREADS;"
+    assert len(re.findall(split, open(os.path.join(SCAN_CSRC, "gf_scan_common.h")).read())) == 1
+    for header, kernels in (("gf_se_kernels.h", ("gf_se_k_scan",)), ("gf_mc_kernels.h", ("gf_mc_k_scan",)),
+                            ("gf_hn_kernels.h", ("gf_hn_k_scan",)),
+                            ("gf_rc_kernels.h", ("gf_rc_k_scan", "gf_rc_k_name_scan"))):
         src = open(os.path.join(SCAN_CSRC, header)).read()
-        assert len(re.findall(r"per = \((?:ntiles|n) \+ GF_SCAN_TOTALS_THREADS - 1\) / GF_SCAN_TOTALS_THREADS;",
-                              src)) == kernels, header
+        assert not re.findall(split, src), header
+        for kernel in kernels:
+            assert len(re.findall(r"__global__[^;{]*?\bvoid %s\(" % kernel, src)) == 1, kernel
 
 
 def test_batch_sizes_cross_the_thresholds():
