@@ -18,7 +18,7 @@ Reference lines restated (relative to /root/reference):
 from __future__ import annotations
 
 from collections import Counter, defaultdict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 K = 16
 CODE = {"A": 0, "T": 1, "C": 2, "G": 3}  # indexer.rs:825-841
@@ -99,7 +99,8 @@ class IndexModel:
         return v  # type: ignore[return-value]
 
     # Appendix A.2
-    def map_read(self, read: str) -> List[Match]:
+    def map_read_trace(self, read: str) -> "Trace":
+        """map_read with the value every gate decided on: the only statement of the algorithm here."""
         L = len(read)
         votes: Counter = Counter()
         for i in range(0, L - K + 1, 2):
@@ -109,8 +110,10 @@ class IndexModel:
         ranked = sorted(votes.items(), key=lambda kv: (-kv[1], kv[0]))
         gp1, count1 = ranked[0] if len(ranked) > 0 else (0, 0)
         gp2, count2 = ranked[1] if len(ranked) > 1 else (0, 0)
+        count3 = ranked[2][1] if len(ranked) > 2 else 0
+        top, diagonals = (count1, count2, count3), (unkey64(gp1), unkey64(gp2))
         if 2 * count1 < 40 or 2 * count2 < 20:
-            return []
+            return Trace(top, diagonals, None, None, None, [])
 
         wclass = [0] * max(0, L - K + 1)
         for i in range(0, L - K + 1):
@@ -132,9 +135,29 @@ class IndexModel:
             lo, hi = max(0, j - K + 1), min(j, L - K)
             if lo <= hi:
                 mask[j] = max(wclass[lo:hi + 1])
-        if sum(1 for m in mask if m <= 1) > 10:
-            return []
-        return segment_mask(mask, unkey64(gp1), unkey64(gp2))
+        unmasked = sum(1 for m in mask if m <= 1)
+        if unmasked > 10:
+            return Trace(top, diagonals, mask, unmasked, None, [])
+        runs = [best_run(mask, target) for target in (3, 2)]
+        return Trace(top, diagonals, mask, unmasked, tuple(e - s for s, e in runs),
+                     segment_mask(mask, diagonals[0], diagonals[1]))
+
+    def map_read(self, read: str) -> List[Match]:
+        return self.map_read_trace(read).segments
+
+    def high_windows(self, read: str) -> int:
+        """Windows of the read whose key has six sites or more (they cannot vote)."""
+        return sum(1 for i in range(len(read) - K + 1) if self.table.get(kmer_at(read, i)) is HIGH)
+
+
+class Trace(NamedTuple):
+    """What map_read decided on, gate by gate; a field is None when an earlier gate ended the read."""
+    votes: Tuple[int, int, int]            # the three highest vote counts
+    diagonals: Tuple[Site, Site]           # first and second place (ties: the smaller key first)
+    mask: Optional[List[int]]              # per base 3 / 2 / 1 / 0, when the vote gate passed
+    unmasked: Optional[int]                # bases with mask <= 1
+    spans: Optional[Tuple[int, int]]       # best run's end - start for target 3, then 2, past the mask gate
+    segments: List[Match]
 
 
 def run_end(mask: Sequence[int], s: int, target: int) -> int:
@@ -153,19 +176,24 @@ def run_end(mask: Sequence[int], s: int, target: int) -> int:
     return end - 1
 
 
+def best_run(mask: Sequence[int], target: int) -> Tuple[int, int]:
+    """Appendix A.3: every start s <= L-2 with mask[s]==target is tried; the first longest run wins
+    ((-1, -1) when there is none)."""
+    best_s, best_e = -1, -1
+    for s in range(0, len(mask) - 1):
+        if mask[s] != target:
+            continue
+        e = run_end(mask, s, target)
+        if e - s > best_e - best_s:
+            best_s, best_e = s, e
+    return best_s, best_e
+
+
 def segment_mask(mask: Sequence[int], gp1: Site, gp2: Site) -> List[Match]:
-    """Appendix A.3: every start s <= L-2 with mask[s]==target is tried; the first
-    longest run wins; it is emitted when end-start > 20."""
-    L = len(mask)
+    """Appendix A.3: the best run of each target is emitted when end-start > 20."""
     out: List[Match] = []
     for target, gp in ((3, gp1), (2, gp2)):
-        best_s, best_e = -1, -1
-        for s in range(0, L - 1):
-            if mask[s] != target:
-                continue
-            e = run_end(mask, s, target)
-            if e - s > best_e - best_s:
-                best_s, best_e = s, e
+        best_s, best_e = best_run(mask, target)
         if best_e - best_s > 20:
             out.append((best_s, best_e, gp[0], gp[1]))
     return out
