@@ -9,6 +9,9 @@ that ``read_pair.scan_pairs_device`` gives, so ``PairScan.download``, ``finish_p
 C ABI (genefuserust_amd/scan_csrc/); it is loaded after ``_lib.lib()`` so that both refer to the one libgfmatch.so of this
 tree.  No CPU fallback: without the libraries and a GPU every compute call raises.
 
+With ``chunk_bytes`` the FASTQ files are streamed once for all CSVs (``_stream_multi_csv``): scan_stream's chunk loop
+with the scan of one chunk against every index plugged in, and the K results handed back in one block (scan_pack.py).
+
 ``multi_csv.py`` (the bare mapping of resident reads over ranks) stays as it is; running this file-level scan on
 several ranks is not done here (``plan_multi_csv`` says which rank would own which CSV).
 """
@@ -16,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from contextlib import ExitStack
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _lib
@@ -153,9 +157,72 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
+def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None):
+    """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
+    ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
+    behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
+    every index with one hand-back: the cut (the full one: gf_mc_pairs_prepare_device takes the qualities at the bases'
+    offsets), pairs prepared once, then per index the scan and the names of its hit records, all queued without a
+    synchronisation; ``scan_pack.pack_scans_device`` over the K results; one ``download``.  An index whose scan or
+    names did not fit is scanned again alone for that chunk (``scan_stream._scan_alone``, with room for everything)."""
+    from . import scan_pack, scan_stream
+    from .fastq import FastqReader
+    from .fusion_mapper import FusionMapper
+    from .read_pair import finish_pair_hits
+    from .scan import named_from_device, route_counters
+    single = len(files) == 1
+    count_key = "reads" if single else "pairs"
+    first_caps = {} if hits_cap is None else dict(hits_cap=int(hits_cap))
+    mappers = [FusionMapper(ix) for ix in indexers]
+    found = [[] for _ in indexers]
+    sums = [{count_key: 0, "merged_pairs": 0, "retried_reads": 0} for _ in indexers]
+    chunks = 0
+
+    def scan_records(ix0, texts, batches, m, done, max_read_len, names):
+        reads = scan_stream._chunk_reads(batches, m, max_read_len)
+        offs, nb, mrl = reads
+        prepared = None
+        if not single:
+            l, r = batches
+            prepared = prepare_pairs_device(ix0, l.bases[:nb[0]], l.quals[:nb[0]], offs[0], r.bases[:nb[1]],
+                                            r.quals[:nb[1]], offs[1], mrl)
+        # (check_lengths: max_read_len is the chunk's longest read, and waiting for a scan's totals is what this avoids)
+        steps = [scan_stream._scan_step(ix, texts, batches, m, done, reads, prepared, check_lengths=False)
+                 for ix in indexers]
+        scans, gathered = [], []
+        for scan, _, gather in steps:
+            scans.append(scan(**first_caps))
+            gathered.append(gather(scans[-1]))
+        out = []
+        for k, u in enumerate(scan_pack.pack_scans_device(scans, gathered).download()):
+            if u.bits & ~scan_pack.OVER_NAMES:   # the scan itself did not fit (or is not one): again, alone, with room
+                if u.bits & scan_pack.BAD_SCAN:
+                    raise _lib.GfError(_lib.GF_ERR_ARG, "scan %d of a chunk does not hold together: %r" % (k, u.totals))
+                out.append(scan_stream._scan_alone(steps[k], steps[k][1], m, single, True))
+            elif u.bits:   # only its names did not fit: gathered again with the size the header asked for
+                rec, hb, hq, tot = scans[k].download()
+                tot[count_key] = m
+                out.append((rec, hb, hq, steps[k][2](scans[k], names_cap=u.name_bytes).download(), tot))
+            else:
+                out.append((u.rec, u.bases, u.quals, u.names, dict(u.totals, **{count_key: m})))
+        return out
+
+    with ExitStack() as opened:
+        sources = [opened.enter_context(FastqReader(f).open_stream()) for f in files]
+        for per_index in scan_stream._scan_source_stream(indexers[0], sources, chunk_bytes, None, True, scan_records,
+                                                         lean=False):
+            for k, (rec, hb, hq, names, tot) in enumerate(per_index):
+                found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names)
+                for key in sums[k]:
+                    sums[k][key] += tot[key]
+            chunks += 1
+    return [(f, *route_counters(count_key, t[count_key], len(f), t, chunks)) for f, t in zip(found, sums)]
+
+
 def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
-                          time: str = "", ref_chunk_bytes: int = None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
+                          hits_cap: int = None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -164,7 +231,17 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     ``json_file`` each entry's ``report_json`` goes to its ``report_names`` name — two entries with the same stem share
     a name and the later one overwrites the earlier, as in the reference.  ``ref_chunk_bytes``: None keeps every
     contig of the FASTA on the host for the whole run; with a value one streamed pass over the FASTA cuts the gene
-    slices of all CSVs on the device (``ref_cut.cut_gene_slices``), and the results are the same."""
+    slices of all CSVs on the device (``ref_cut.cut_gene_slices``), and the results are the same.
+
+    ``chunk_bytes``: None reads the FASTQ files whole and keeps the records resident while one index after the other is
+    built, scanned and closed.  With a value the files are streamed once, in chunks of that many bytes of plain text
+    (``_stream_multi_csv``): every index is built up front and stays open for the pass — 0.15 GB of HBM for an index of
+    the druggable panel's shape, 0.5 GB for one of the cancer panel's, times the number of list entries,
+    a CSV named twice counting twice — each chunk is cut and its pairs prepared once, scanned against every index, and
+    handed back in one block (scan_pack.py): two read-backs per chunk, however many CSVs.  Neither the host nor HBM
+    ever holds a file; results and counters are those of the single-CSV streamed scan of each CSV, ``chunks``
+    included.  ``hits_cap`` (streamed only): the record capacity of a chunk's first scan per CSV (default: the
+    library's, at least 1024); a CSV with more hits in a chunk is scanned again alone for that chunk."""
     from .fastq import FastqReader, FastqReaderPair
     from .fusion_mapper import FusionMapper
     from .indexer import Fusion
@@ -180,6 +257,18 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
         refs = [GeneSlices(s) for s in cut_gene_slices(ref_file, [Fusion.parse_csv(c) for c in csvs], ref_chunk_bytes,
                                                        device)]
     out: List[Tuple[str, List[FusionResult], dict]] = []
+    if chunk_bytes is not None:
+        with ExitStack() as stack:
+            opened = [stack.enter_context(open_index(refs[k], csv, device)) for k, csv in enumerate(csvs)]
+            files = (read1_file, read2_file) if read2_file else (read1_file,)
+            produced = _stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap) if opened else []
+            for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
+                kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after)
+                out.append((csv, *report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings)))
+        for name, (_, results, _) in zip(names, out):
+            with open(name, "w") as f:
+                f.write(report_json(results, command, version, time, settings))
+        return out
     reads = prepared = None
     for k, csv in enumerate(csvs):
         with open_index(refs[k], csv, device) as (ix, fusions):
@@ -213,8 +302,8 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
     gives ``scan_multi_csv_report``'s list.  ``chunk_bytes`` streams the FASTQ files of the single-CSV scanners
-    (``scan.scan_pair_end_files``); multi-CSV mode keeps its reads resident, as the reference does, and raises
-    ``ValueError`` for it.  ``ref_chunk_bytes`` streams the reference FASTA in every mode (``scan.open_index``,
+    (``scan.scan_pair_end_files``); for a list of CSVs this switch raises ``ValueError`` — multi-CSV mode streams its
+    files through ``scan_multi_csv_report(chunk_bytes=...)``, called directly.  ``ref_chunk_bytes`` streams the reference FASTA in every mode (``scan.open_index``,
     ``scan_multi_csv_report``)."""
     from . import scan
     if _rust_stem_ext(fusion_file)[2] == "csv":
@@ -229,6 +318,7 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
                 f.write(report_json(results, command, version, time, settings))
         return results, counters
     if chunk_bytes is not None:
-        raise ValueError("chunk_bytes: multi-CSV mode scans resident reads once per CSV and does not stream them")
+        raise ValueError("chunk_bytes: this switch keeps the reads of multi-CSV mode resident; call "
+                         "scan_multi_csv_report(chunk_bytes=...) to stream them")
     return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
                                  version, time, ref_chunk_bytes)

@@ -31,19 +31,6 @@ GfRcText text_of(const void* d_text, int64_t text_bytes) {
   return GfRcText{(const uint8_t*)(p & ~(uintptr_t)(GF_RC_PIECE - 1)), (int64_t)(p & (GF_RC_PIECE - 1)), text_bytes};
 }
 
-// the device a pointer's memory is on; anything but device memory is refused
-int device_of(const void* p, const char* what, int& dev) {
-  hipPointerAttribute_t a;
-  if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(GF_ERR_NO_DEVICE, std::string(what) + " is not device memory (there is no CPU fallback)");
-  }
-  if (a.type != hipMemoryTypeDevice)
-    return fail(GF_ERR_NO_DEVICE, std::string(what) + " is not device memory (there is no CPU fallback)");
-  dev = a.device;
-  return GF_OK;
-}
-
 }  // namespace
 
 extern "C" {

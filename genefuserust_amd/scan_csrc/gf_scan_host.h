@@ -1,6 +1,6 @@
-// What the host sides of libgfse.so (gf_single_end.hip) and libgfmcsv.so (gf_multi_csv.hip) share.  Each library is
-// one translation unit that includes this header once, so everything here is file-local, and each library has its
-// own thread-local error string behind its own gf_se_last_error / gf_mc_last_error.
+// What the host sides of the companion libraries (gf_single_end.hip, gf_multi_csv.hip, gf_hit_names.hip, gf_ref_cut.hip,
+// gf_scan_pack.hip) share.  Each library is one translation unit that includes this header once, so everything here is
+// file-local, and each library has its own thread-local error string behind its own gf_*_last_error.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,6 +39,20 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+// the device a pointer's memory is on, for the libraries that take no gf_index (libgfrefcut.so, libgfpack.so);
+// anything but device memory is refused
+int device_of(const void* p, const char* what, int& dev) {
+  hipPointerAttribute_t a;
+  if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(GF_ERR_NO_DEVICE, std::string(what) + " is not device memory (there is no CPU fallback)");
+  }
+  if (a.type != hipMemoryTypeDevice)
+    return fail(GF_ERR_NO_DEVICE, std::string(what) + " is not device memory (there is no CPU fallback)");
+  dev = a.device;
+  return GF_OK;
+}
 
 // Buffers are carved in 256-byte aligned pieces from the caller's base, aligned to 256 bytes first: every layout ends
 // with 256 bytes of room for that.

@@ -51,44 +51,66 @@ def _record_cuts(batches, texts, final, side_names):
     return m, counts, cuts
 
 
-def _scan_records(indexer: Indexer, texts, batches, m: int, done: int, max_read_len: Optional[int], names: bool):
-    """The first ``m`` records of every side scanned (``scan_with_room``), the names of the hit records gathered behind
-    the scan: (records, hit bases, hit qualities, names or None, totals)."""
+def _chunk_reads(batches, m: int, max_read_len: Optional[int]):
+    """(offsets, base bytes, max_read_len) of the first ``m`` records of every side.  ``max_read_len`` None: the longest
+    read of the chunk, as the whole-file scans take the longest of the file."""
+    offs = [b.offsets[:m + 1] for b in batches]
+    nb = [int(o[-1].item()) for o in offs]
+    mrl = max_read_len
+    if mrl is None:
+        mrl = max([int((o[1:] - o[:-1]).max().item()) for o in offs] + [1])
+    return offs, nb, mrl
+
+
+def _scan_step(indexer: Indexer, texts, batches, m: int, done: int, reads, prepared=None, check_lengths: bool = True):
+    """How the first ``m`` records of every side (``reads``: what ``_chunk_reads`` gave) are scanned against one index:
+    (``scan(**caps)`` -> ``PairScan``, the capacities with room for everything, ``gather(res, **cap)`` -> the
+    ``HitNames`` of a scan's records).  ``prepared``: the ``PreparedPairs`` of these pairs (multi_csv_scan.py), scanned
+    in place of the records themselves."""
     from .fastq import fastq_cut_device
     from .hit_names import hit_names_device
     from .single_end import scan_single_device
     single = len(texts) == 1
-    offs = [b.offsets[:m + 1] for b in batches]
-    nb = [int(o[-1].item()) for o in offs]
-    mrl = max_read_len
-    if mrl is None:   # the longest read of the chunk, as the whole-file scans take the longest of the file
-        mrl = max([int((o[1:] - o[:-1]).max().item()) for o in offs] + [1])
+    offs, nb, mrl = reads
     if single:
         b = batches[0]
 
         def scan(**caps):
-            return scan_single_device(indexer, b.bases[:nb[0]], b.quals[:nb[0]], offs[0], mrl, read_id_base=done, **caps)
+            return scan_single_device(indexer, b.bases[:nb[0]], b.quals[:nb[0]], offs[0], mrl, read_id_base=done,
+                                      check_lengths=check_lengths, **caps)
         room = dict(hits_cap=m, bytes_cap=nb[0] + 64, retry_cap=m)
     else:
-        l, r = batches
-        lean = l.qual_off is not None and r.qual_off is not None
-        if not lean:   # one side has a quality line of another length than its sequence: both the full way
-            l = l if l.qual_off is None else fastq_cut_device(indexer, texts[0])
-            r = r if r.qual_off is None else fastq_cut_device(indexer, texts[1])
-        lq, rq = (l.quals, r.quals) if lean else (l.quals[:nb[0]], r.quals[:nb[1]])
-        qo = dict(l_qual_off=l.qual_off[:m], r_qual_off=r.qual_off[:m]) if lean else {}
-
-        def scan(**caps):
-            return scan_pairs_device(indexer, l.bases[:nb[0]], lq, offs[0], r.bases[:nb[1]], rq, offs[1], mrl,
-                                     pair_id_base=done, **caps, **qo)
         room = dict(hits_cap=3 * m, bytes_cap=2 * sum(nb) + 64, retry_cap=3 * m)
+        if prepared is not None:
+            from .multi_csv_scan import scan_prepared_pairs_device
+
+            def scan(**caps):
+                return scan_prepared_pairs_device(indexer, prepared, pair_id_base=done, **caps)
+        else:
+            l, r = batches
+            lean = l.qual_off is not None and r.qual_off is not None
+            if not lean:   # one side has a quality line of another length than its sequence: both the full way
+                l = l if l.qual_off is None else fastq_cut_device(indexer, texts[0])
+                r = r if r.qual_off is None else fastq_cut_device(indexer, texts[1])
+            lq, rq = (l.quals, r.quals) if lean else (l.quals[:nb[0]], r.quals[:nb[1]])
+            qo = dict(l_qual_off=l.qual_off[:m], r_qual_off=r.qual_off[:m]) if lean else {}
+
+            def scan(**caps):
+                return scan_pairs_device(indexer, l.bases[:nb[0]], lq, offs[0], r.bases[:nb[1]], rq, offs[1], mrl,
+                                         pair_id_base=done, **caps, **qo)
 
     def gather(res, **cap):
         return hit_names_device(indexer, res, texts[0], batches[0], *(() if single else (texts[1], batches[1])),
-                                pair_id_base=done, **cap) if names else None
-    # (first with the library's default capacities; the names are queued behind the scan: the record count
-    #  stays on the device)
-    res, nm, out = scan_with_room(scan, {}, room, gather)
+                                pair_id_base=done, **cap)
+    return scan, room, gather
+
+
+def _scan_alone(step, first_caps: dict, m: int, single: bool, names: bool):
+    """One index's scan of a chunk with a read-back of its own (``scan_with_room``: ``first_caps``, then the room), the
+    names of the hit records gathered behind the scan: (records, hit bases, hit qualities, names or None, totals)."""
+    scan, room, gather = step
+    # (the names are queued behind the scan: the record count stays on the device)
+    res, nm, out = scan_with_room(scan, first_caps, room, gather if names else None)
     name_list = None
     if names:
         _, need, over, _ = (int(x) for x in nm.totals.cpu())
@@ -99,15 +121,25 @@ def _scan_records(indexer: Indexer, texts, batches, m: int, done: int, max_read_
     return out[0], out[1], out[2], name_list, out[3]
 
 
-def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool):
-    """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned.  The result
-    is (what the stream yields for the chunk or None, records scanned, whether the scan ends here)."""
+def _scan_records(indexer: Indexer, texts, batches, m: int, done: int, max_read_len: Optional[int], names: bool):
+    """The first ``m`` records of every side scanned — first with the library's default capacities — and the names of
+    the hit records: (records, hit bases, hit qualities, names or None, totals)."""
+    step = _scan_step(indexer, texts, batches, m, done, _chunk_reads(batches, m, max_read_len))
+    return _scan_alone(step, {}, m, len(texts) == 1, names)
+
+
+def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
+                scan_records=_scan_records, lean: Optional[bool] = None):
+    """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
+    ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
+    ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do)."""
     from .fastq import fastq_cut_device
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
-    batches = [fastq_cut_device(indexer, t, lean=len(texts) > 1) for t in texts]
+    lean = len(texts) > 1 if lean is None else lean
+    batches = [fastq_cut_device(indexer, t, lean=lean) for t in texts]
     m, counts, cuts = _record_cuts(batches, texts, final, side_names)
-    out = _scan_records(indexer, texts, batches, m, done, max_read_len, names) if m > 0 else None
+    out = scan_records(indexer, texts, batches, m, done, max_read_len, names) if m > 0 else None
     # records pair up by position and the shorter file ends both (fastq_reader.rs:209-218): stop when a side that
     # has all its bytes has no record left
     last = any(f and c == m for f, c in zip(final, counts))
@@ -115,9 +147,11 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     return cuts, [c == m for c in counts], (out, m, last)
 
 
-def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool):
-    """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk (records, hit bases, hit
-    qualities, names or None, totals)."""
+def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
+                        scan_records=_scan_records, lean: Optional[bool] = None):
+    """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
+    for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
+    of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``)."""
     import torch
     h = indexer._handle()
 
@@ -127,7 +161,7 @@ def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_le
     side_names = [s.name for s in stream.sides]
     done = 0
     with closing(stream.run(lambda texts, final: _scan_chunk(indexer, side_names, texts, final, done, max_read_len,
-                                                             names))) as chunks:
+                                                             names, scan_records, lean))) as chunks:
         for out, m, last in chunks:
             if out is not None:
                 yield out
