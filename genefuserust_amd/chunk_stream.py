@@ -3,6 +3,7 @@ the reference cut (ref_cut.py).
 
     byte sources (files, gunzipped as they are read; texts in memory)  --readinto, upload threads-->  pinned staging
     blocks  --H2D, copy stream-->  device text buffers (behind the carried-over tail of the previous chunk)  -->
+    (or: BGZF files, compressed as they are  -->  staging blocks  --H2D-->  inflated into the text buffers: bgzf.py)
     the consumer's ``process(texts, final)`` on the processing stream  -->  how many bytes of each text are done with.
 
 ``ChunkStream`` owns the streams, the slots, the threads and the carries; what a chunk means, and when to stop before the
@@ -20,6 +21,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from .bgzf import DeviceInflate
 
 CARRY_MAX = 1 << 20  # bytes kept in front of a chunk for the previous chunk's tail
 
@@ -90,26 +92,31 @@ def checked_chunk_bytes(chunk_bytes) -> int:
 class Side:
     """The host half of one text: a byte source — anything with ``readinto(memoryview) -> int``, 0 at the end — and the
     two staging blocks its chunks are read into: pinned ones of ``gf_host_alloc``, or the writable ``views`` given (a
-    test's bytearrays).  A source that lends its bytes (``take``) needs none."""
+    test's bytearrays).  A source that lends its bytes (``take``) needs none.  A source whose staged bytes are inflated
+    on the device (``stage_compressed``, bgzf.BgzfSource) stages compressed bytes, whole members, in blocks of the size
+    it asks for, and says how the chunk's text is put together (``chunks[slot]``)."""
 
     def __init__(self, source, chunk_bytes: int, views=None):
         self.source = source
         self.name = getattr(source, "name", "<stream>")
         self.lends = hasattr(source, "take")
+        self.inflates = hasattr(source, "stage_compressed")
         self.chunk_len = [0, 0]
+        self.chunks: list = [None, None]   # (an inflating source's bgzf.Chunk per slot)
         self.eof = False      # the source's last byte is in a chunk staged so far
         self.ahead = b""      # the byte read past a full chunk to see whether the source has ended
         self.staging: List[int] = []
         self.views: list = [] if views is None else list(views)
         if views is None and not self.lends:
             L = _lib.lib()
+            block = source.staging_bytes(chunk_bytes) if self.inflates else chunk_bytes
             for _ in range(2):
-                p = L.gf_host_alloc(chunk_bytes)
+                p = L.gf_host_alloc(block)
                 if not p:
                     self.close()
-                    raise _lib.GfError(_lib.GF_ERR_HIP, "gf_host_alloc(%d) failed" % chunk_bytes)
+                    raise _lib.GfError(_lib.GF_ERR_HIP, "gf_host_alloc(%d) failed" % block)
                 self.staging.append(p)
-                self.views.append(memoryview((C.c_uint8 * chunk_bytes).from_address(p)).cast("B"))
+                self.views.append(memoryview((C.c_uint8 * block).from_address(p)).cast("B"))
 
     def close(self) -> None:
         self.views = []
@@ -123,11 +130,15 @@ class Side:
         thread: reading (and gunzipping) blocks that thread only."""
         ptr, n = None, 0
         if self.eof:
-            pass
+            self.chunks[slot] = None
         elif self.lends:
             src = self.source.take(nbytes)
             ptr, n = src.ctypes.data, int(src.size)
             self.eof = self.source.at_end()
+        elif self.inflates:     # (ptr, n: the compressed bytes staged; chunk_len is the text's)
+            c = self.chunks[slot] = self.source.stage_compressed(self.views[slot], nbytes)
+            self.chunk_len[slot], self.eof = c.text_len, c.final
+            return (self.staging[slot] if self.staging else None), c.comp_len
         else:
             n, self.ahead, self.eof = read_chunk(self.source, self.views[slot], nbytes, self.ahead)
             ptr = self.staging[slot] if self.staging else None
@@ -159,11 +170,16 @@ class ChunkStream:
         self.bufs: list = []          # per side, per slot
         self.carry_len: List[int] = []
         self.starved: List[bool] = []
+        self.inflate: list = []       # per side: its bgzf.DeviceInflate, or None
         try:
             for src in sources:
-                self.bufs.append([torch.empty(CARRY_MAX + chunk_bytes + 64, dtype=torch.uint8, device=dev)
+                inflates = hasattr(src, "stage_compressed")
+                # (an inflated chunk's last member is written whole: up to 64 KiB of room behind the chunk)
+                room = (1 << 16) if inflates else 0
+                self.bufs.append([torch.empty(CARRY_MAX + chunk_bytes + 64 + room, dtype=torch.uint8, device=dev)
                                   for _ in range(2)])
                 self.sides.append(Side(src, chunk_bytes))
+                self.inflate.append(DeviceInflate(src, chunk_bytes, dev) if inflates else None)
                 self.carry_len.append(0)
                 self.starved.append(True)
         except BaseException:
@@ -198,7 +214,10 @@ class ChunkStream:
 
         def one(k: int):
             ptr, n = self.sides[k].stage(slot, nbytes[k])
-            if n:
+            if self.sides[k].chunks[slot] is not None:
+                self.inflate[k].upload(slot, self.sides[k].chunks[slot], ptr, self.bufs[k][slot][CARRY_MAX:],
+                                       self.copy_stream)
+            elif n:
                 self.copy(ptr, self.bufs[k][slot].data_ptr() + CARRY_MAX, n, self.copy_stream.cuda_stream)
 
         def run():

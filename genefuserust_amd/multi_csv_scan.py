@@ -157,7 +157,7 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
-def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None):
+def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host"):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
@@ -166,7 +166,6 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     synchronisation; ``scan_pack.pack_scans_device`` over the K results; one ``download``.  An index whose scan or
     names did not fit is scanned again alone for that chunk (``scan_stream._scan_alone``, with room for everything)."""
     from . import scan_pack, scan_stream
-    from .fastq import FastqReader
     from .fusion_mapper import FusionMapper
     from .read_pair import finish_pair_hits
     from .scan import named_from_device, route_counters
@@ -208,7 +207,7 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
         return out
 
     with ExitStack() as opened:
-        sources = [opened.enter_context(FastqReader(f).open_stream()) for f in files]
+        sources = scan_stream.open_fastq_sources(opened, files, inflate)
         for per_index in scan_stream._scan_source_stream(indexers[0], sources, chunk_bytes, None, True, scan_records,
                                                          lean=False):
             for k, (rec, hb, hq, names, tot) in enumerate(per_index):
@@ -222,7 +221,7 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
 def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
-                          hits_cap: int = None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          hits_cap: int = None, inflate: str = "host") -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -241,13 +240,17 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     handed back in one block (scan_pack.py): two read-backs per chunk, however many CSVs.  Neither the host nor HBM
     ever holds a file; results and counters are those of the single-CSV streamed scan of each CSV, ``chunks``
     included.  ``hits_cap`` (streamed only): the record capacity of a chunk's first scan per CSV (default: the
-    library's, at least 1024); a CSV with more hits in a chunk is scanned again alone for that chunk."""
+    library's, at least 1024); a CSV with more hits in a chunk is scanned again alone for that chunk.
+
+    ``inflate``: where the streamed ``.gz`` files are inflated — the FASTQ files with ``chunk_bytes``, the reference
+    with ``ref_chunk_bytes`` — "host", "auto" or "device": see ``scan.scan_pair_end_files``."""
     from .fastq import FastqReader, FastqReaderPair
     from .fusion_mapper import FusionMapper
     from .indexer import Fusion
-    from .scan import (GeneSlices, finish_matches, open_index, pairs_found, read_contigs, report_matches,
-                       single_end_found)
+    from .scan import (GeneSlices, _route_inflate, finish_matches, open_index, pairs_found, read_contigs,
+                       report_matches, single_end_found)
     settings = settings or Settings()
+    fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
     csvs = read_csv_list(csv_list_file)
     names = report_names(json_file, csvs)
     if ref_chunk_bytes is None:
@@ -255,13 +258,14 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     else:
         from .ref_cut import cut_gene_slices
         refs = [GeneSlices(s) for s in cut_gene_slices(ref_file, [Fusion.parse_csv(c) for c in csvs], ref_chunk_bytes,
-                                                       device)]
+                                                       device, ref_inflate)]
     out: List[Tuple[str, List[FusionResult], dict]] = []
     if chunk_bytes is not None:
         with ExitStack() as stack:
             opened = [stack.enter_context(open_index(refs[k], csv, device)) for k, csv in enumerate(csvs)]
             files = (read1_file, read2_file) if read2_file else (read1_file,)
-            produced = _stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap) if opened else []
+            produced = (_stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap, fq_inflate)
+                        if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after)
                 out.append((csv, *report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings)))
@@ -297,22 +301,25 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
 def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
-                chunk_bytes: int = None, ref_chunk_bytes: int = None):
+                chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host"):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
     gives ``scan_multi_csv_report``'s list.  ``chunk_bytes`` streams the FASTQ files of the single-CSV scanners
     (``scan.scan_pair_end_files``); for a list of CSVs this switch raises ``ValueError`` — multi-CSV mode streams its
     files through ``scan_multi_csv_report(chunk_bytes=...)``, called directly.  ``ref_chunk_bytes`` streams the reference FASTA in every mode (``scan.open_index``,
-    ``scan_multi_csv_report``)."""
+    ``scan_multi_csv_report``).  ``inflate``: where the streamed ``.gz`` files are inflated, in every mode
+    (``scan.scan_pair_end_files``)."""
     from . import scan
     if _rust_stem_ext(fusion_file)[2] == "csv":
         if read2_file:
             results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings,
-                                                          chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes)
+                                                          chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
+                                                          inflate=inflate)
         else:
             results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings,
-                                                            chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes)
+                                                            chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
+                                                            inflate=inflate)
         if json_file:
             with open(json_file, "w") as f:
                 f.write(report_json(results, command, version, time, settings))
@@ -321,4 +328,4 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         raise ValueError("chunk_bytes: this switch keeps the reads of multi-CSV mode resident; call "
                          "scan_multi_csv_report(chunk_bytes=...) to stream them")
     return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
-                                 version, time, ref_chunk_bytes)
+                                 version, time, ref_chunk_bytes, inflate=inflate)

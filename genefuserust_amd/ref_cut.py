@@ -325,13 +325,14 @@ def _index_with_room(text, caps: dict) -> Tuple[RefIndex, ChunkRecords]:
 
 
 def cut_gene_slices(ref_file: str, fusion_lists: Sequence[Sequence[Fusion]], chunk_bytes: int,
-                    device: int = -1) -> List[List[Optional[bytes]]]:
+                    device: int = -1, inflate: str = "host") -> List[List[Optional[bytes]]]:
     """Per fusion list, per gene, what ``resolve_gene_slice(read_contigs(ref_file), gene)`` gives — one pass over the
     FASTA serves all lists — with the file read, gunzipped and uploaded in chunks of ``chunk_bytes`` of plain text
     while the device indexes and gathers the previous chunk.  The host holds two pinned staging blocks of
     ``chunk_bytes`` and the wanted bytes, the device two text buffers.  ``device``: -1 is the current one.  Raises as
     the host reader does: ``IsADirectoryError``, ``ValueError`` for an empty file, ``IndexError`` for a range outside
-    its contig; ``GfError(GF_ERR_CAPACITY)`` for a record name of more than 1 MiB."""
+    its contig; ``GfError(GF_ERR_CAPACITY)`` for a record name of more than 1 MiB.  ``inflate``: "host" gunzips a ``.gz``
+    file on the host; "auto" / "device" send a BGZF file's compressed bytes to the device (bgzf.py, ``scan.open_index``)."""
     import torch
     ref_file = str(ref_file)
     chunk_bytes = checked_chunk_bytes(chunk_bytes)
@@ -357,7 +358,8 @@ def cut_gene_slices(ref_file: str, fusion_lists: Sequence[Sequence[Fusion]], chu
             raise GfError(GF_ERR_CAPACITY, "%s: a record name of more than %d bytes" % (ref_file, CARRY_MAX))
         return [nbytes], [True], None
 
-    with FastqByteStream(ref_file, ref_file.endswith(".gz")) as source:
+    from .bgzf import open_source
+    with open_source(ref_file, inflate, lambda: FastqByteStream(ref_file, ref_file.endswith(".gz"))) as source:
         for _ in ChunkStream([source], chunk_bytes, dev, copy, whole_read_sizes).run(cut):
             pass
     return plan.finish()

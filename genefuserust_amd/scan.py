@@ -38,17 +38,23 @@ class GeneSlices(list):
 
 
 @contextmanager
-def open_index(ref, fusion_csv: str, device: int = -1, ref_chunk_bytes: int = None):
+def open_index(ref, fusion_csv: str, device: int = -1, ref_chunk_bytes: int = None, inflate: str = "host"):
     """FASTA (a file name, the contigs ``read_contigs`` gave, or the ``GeneSlices`` of this CSV) + fusion CSV -> (the
     open ``Indexer`` with its index made, the parsed fusions); the index is closed on the way out.
 
     ``ref_chunk_bytes`` (with a file name): None reads the FASTA whole on the host (``read_contigs``).  With a value
     the file is streamed in chunks of that many bytes of plain text and the gene slices are cut out on the device
-    (``ref_cut.cut_gene_slices``): the same index, and no contigs on the host (``Indexer.m_reference`` is None)."""
+    (``ref_cut.cut_gene_slices``): the same index, and no contigs on the host (``Indexer.m_reference`` is None).
+
+    ``inflate`` (with ``ref_chunk_bytes``; ``ValueError`` without): "host" gunzips a ``.gz`` file on the host as it is
+    read; "auto" sends a BGZF file's compressed bytes to the device and inflates them there (bgzf.py), any other file
+    as "host" does; "device" does so too and raises ``ValueError`` for a ``.gz`` file that is not BGZF."""
+    from .bgzf import need_chunks
+    need_chunks(inflate, ref_chunk_bytes is not None, "ref_chunk_bytes")
     fusions = Fusion.parse_csv(fusion_csv)
     if isinstance(ref, str) and ref_chunk_bytes is not None:
         from .ref_cut import cut_gene_slices
-        ref = GeneSlices(cut_gene_slices(ref, [fusions], ref_chunk_bytes, device)[0])
+        ref = GeneSlices(cut_gene_slices(ref, [fusions], ref_chunk_bytes, device, inflate)[0])
     if isinstance(ref, GeneSlices):
         ix = Indexer(None, fusions, device, gene_slices=ref)
     else:
@@ -155,17 +161,18 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes) -> Tuple[List[R
     return (found, *route_counters("reads", b.n_records, len(found)))
 
 
-def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int) -> Tuple[List[ReadMatch], dict, dict]:
+def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int,
+                   inflate: str = "host") -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
-    order, each named from its chunk's device-gathered names, and their counters."""
-    from .scan_stream import scan_pair_source_stream, scan_single_text_stream
+    order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``."""
+    from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
     count_key = "pairs" if len(files) == 2 else "reads"
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
     found: List[ReadMatch] = []
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
     chunks = 0
     with ExitStack() as opened:
-        sources = [opened.enter_context(FastqReader(f).open_stream()) for f in files]
+        sources = open_fastq_sources(opened, files, inflate)
         for rec, hb, hq, names, tot in stream(ix, *sources, chunk_bytes, max_read_len=None):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names)
             for k in sums:
@@ -174,16 +181,25 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int) -
     return (found, *route_counters(count_key, sums[count_key], len(found), sums, chunks))
 
 
+def _route_inflate(inflate, chunk_bytes, ref_chunk_bytes):
+    """(``inflate`` for the FASTQ files, for the reference): it applies where a file is streamed, and raises
+    ``ValueError`` where none is."""
+    from .bgzf import need_chunks
+    need_chunks(inflate, chunk_bytes is not None or ref_chunk_bytes is not None, "chunk_bytes or ref_chunk_bytes")
+    return (inflate if chunk_bytes is not None else "host"), (inflate if ref_chunk_bytes is not None else "host")
+
+
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
-                      chunk_bytes, ref_chunk_bytes=None):
+                      chunk_bytes, ref_chunk_bytes=None, inflate="host"):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
                          "reference")
-    with open_index(ref_file, fusion_csv, device, ref_chunk_bytes) as (ix, fusions):
+    fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
+    with open_index(ref_file, fusion_csv, device, ref_chunk_bytes, ref_inflate) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
-            produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes)
+            produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate)
         else:
             reads = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
             (l, _), (r, _) = reads
@@ -197,7 +213,8 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
 
 def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                         deletion_threshold: int = 50, remove_alignables: bool = False,
-                        chunk_bytes: int = None, ref_chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
+                        chunk_bytes: int = None, ref_chunk_bytes: int = None,
+                        inflate: str = "host") -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -208,34 +225,45 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
 
     ``ref_chunk_bytes``: None reads the reference FASTA whole on the host.  With a value it is streamed in chunks too
     and the gene slices are cut out on the device (``open_index``); matches and counters are the same.
-    ``remove_alignables`` needs whole contigs and raises ``ValueError`` with it."""
+    ``remove_alignables`` needs whole contigs and raises ``ValueError`` with it.
+
+    ``inflate``: where ``.gz`` files that are streamed are inflated — the FASTQ files with ``chunk_bytes``, the
+    reference with ``ref_chunk_bytes``; ``ValueError`` for anything but "host" with neither.  "host" (the default):
+    gunzipped on the host as they are read.  "auto": a file whose first member is BGZF (bgzip's and the sequencers'
+    format) goes to the device compressed and is inflated there (bgzf.py); any other file as "host" does.  "device":
+    as "auto", but a ``.gz`` file that is not BGZF raises ``ValueError``.  Matches and counters are the same; a member
+    that fails raises ``gzip.BadGzipFile``, a file that ends inside a member ``EOFError``, a member that is not BGZF
+    behind the first ``ValueError``."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
-                             remove_alignables, chunk_bytes, ref_chunk_bytes)[:2]
+                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
-                         settings: Settings = None, chunk_bytes: int = None,
-                         ref_chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
+                         settings: Settings = None, chunk_bytes: int = None, ref_chunk_bytes: int = None,
+                         inflate: str = "host") -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` of fusion_result.py turn the list into
-    the reference's stdout block and JSON file.  ``chunk_bytes``, ``ref_chunk_bytes``: see ``scan_pair_end_files``."""
+    the reference's stdout block and JSON file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``: see
+    ``scan_pair_end_files``."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
-                                             settings.deletion_threshold, False, chunk_bytes, ref_chunk_bytes), settings)
+                                             settings.deletion_threshold, False, chunk_bytes, ref_chunk_bytes, inflate),
+                          settings)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                        ref_chunk_bytes=None):
+                        ref_chunk_bytes=None, inflate="host"):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
     if chunk_bytes is not None and route != "device":
         raise ValueError("chunk_bytes streams the file through the device route; route=%r reads it whole" % (route,))
-    with open_index(ref_file, fusion_csv, device, ref_chunk_bytes) as (ix, fusions):
+    fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
+    with open_index(ref_file, fusion_csv, device, ref_chunk_bytes, ref_inflate) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
-            produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes)
+            produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate)
         elif route == "device":
             produced = single_end_found(ix, mapper, *FastqReader(read1_file).read_all_device(ix))
         else:
@@ -246,7 +274,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
 
 def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                           deletion_threshold: int = 50, route: str = "device",
-                          chunk_bytes: int = None, ref_chunk_bytes: int = None) -> Tuple[List[ReadMatch], dict]:
+                          chunk_bytes: int = None, ref_chunk_bytes: int = None,
+                          inflate: str = "host") -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -257,16 +286,17 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
 
     ``chunk_bytes`` (device route only): None reads the file whole; with a value it is streamed in chunks of that many
     bytes of plain text (scan_stream.scan_single_text_stream), as in ``scan_pair_end_files``; the counters add
-    ``chunks``.  ``ref_chunk_bytes`` (either route): the reference FASTA in chunks, see ``scan_pair_end_files``."""
+    ``chunks``.  ``ref_chunk_bytes`` (either route): the reference FASTA in chunks, see ``scan_pair_end_files``.
+    ``inflate``: where the streamed ``.gz`` files are inflated, see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                               ref_chunk_bytes)[:2]
+                               ref_chunk_bytes, inflate)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                            settings: Settings = None, route: str = "device", chunk_bytes: int = None,
-                           ref_chunk_bytes: int = None) -> Tuple[List[FusionResult], dict]:
+                           ref_chunk_bytes: int = None, inflate: str = "host") -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``: see ``scan_single_end_files``."""
+    ``ref_chunk_bytes``, ``inflate``: see ``scan_single_end_files``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
-                                               route, chunk_bytes, ref_chunk_bytes), settings)
+                                               route, chunk_bytes, ref_chunk_bytes, inflate), settings)

@@ -170,12 +170,25 @@ def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_le
                 break
 
 
+def open_fastq_sources(opened, files, inflate: str = "host") -> list:
+    """The byte sources of the FASTQ ``files``, entered into the ``ExitStack`` ``opened``: ``FastqReader.open_stream``,
+    or with ``inflate`` "auto" / "device" a ``bgzf.BgzfSource`` for a BGZF file, whose compressed bytes are inflated on
+    the device."""
+    from .bgzf import open_source
+    from .fastq import FastqReader
+    sources = []
+    for f in files:
+        reader = FastqReader(f)
+        sources.append(opened.enter_context(open_source(reader.m_filename, inflate, reader.open_stream)))
+    return sources
+
+
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320,
                             names: bool = True) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
-    the end): ``ArraySource``, ``fastq.FastqReader.open_stream()`` — chunk by chunk.  Yields, per chunk, (gf_pair_hit
-    records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
+    the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
+    per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
     the records' reads (``hit_names_device``; None with ``names=False``), totals); ``totals["pairs"]`` is the chunk's
     pair count.  Records pair up by position; the shorter file ends both (fastq_reader.rs:209-218).  The next chunk of
     each source is read (gunzipped) and uploaded on host threads while the device works on the current one; the host
