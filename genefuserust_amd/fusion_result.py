@@ -4,8 +4,12 @@ into fusion candidates, the break-point refinement, qualification and the text /
 ``FusionResult``, src/core/fusion_result.rs:24-511 and :761-798; ``ReadMatch::print``,
 src/core/read_match.rs:153-186; ``JsonReporter::run``, src/core/json_reporter.rs:34-123).
 
-Host logic on a handful of reads per run (the reference keeps it on the CPU as well); the only
-compute is the edit distance, which is ``gf_edit_distance`` of libgfmatch.so.  Where the
+Host logic, as the reference keeps it on the CPU; the only compute is the edit distance, which is
+``gf_edit_distance`` of libgfmatch.so.  That is one library call per comparison, filter and distance,
+and ``support`` scans every match of every cluster: fine for the handful of matches of a small run, not
+for the 10^5 of a full batch or the thousands of reads a deep panel puts on one junction.  For those,
+``report_tail.py`` does the same steps in bulk (libgfreport.so); ``cluster_with`` below is the one body
+both share.  Where the
 reference would panic (``subchars`` beyond a string's end) this raises ``IndexError``.
 The HTML report (protein diagrams) is not here.
 """
@@ -144,20 +148,24 @@ class FusionResult:
         right_ed = edit_distance(_take(right_seq, 0, rc), _take(self.m_right_ref, 0, rc))
         return total, left_ed, right_ed
 
+    def best_shift(self, m: ReadMatch):  # :299-324 for one match -> (shift, left distance, right distance)
+        smallest, shift = 0xFFFF, 0
+        ld, rd = m.m_left_distance, m.m_right_distance
+        for s in range(-3, 4):
+            ed, l_ed, r_ed = self.calc_ed(m, s)
+            if ed < smallest:
+                smallest, shift, ld, rd = ed, s, l_ed, r_ed
+        return shift, ld, rd
+
+    @staticmethod
+    def shifted(m: ReadMatch, shift: int, ld: int, rd: int) -> ReadMatch:
+        return replace(m, m_read_break=m.m_read_break + shift,
+                       m_left_gp=GenePos(m.m_left_gp.contig, m.m_left_gp.position + shift),
+                       m_right_gp=GenePos(m.m_right_gp.contig, m.m_right_gp.position + shift),
+                       m_left_distance=ld, m_right_distance=rd)
+
     def adjust_fusion_break(self) -> None:  # :299-324
-        out = []
-        for m in self.m_matches:
-            smallest, shift = 0xFFFF, 0
-            ld, rd = m.m_left_distance, m.m_right_distance
-            for s in range(-3, 4):
-                ed, l_ed, r_ed = self.calc_ed(m, s)
-                if ed < smallest:
-                    smallest, shift, ld, rd = ed, s, l_ed, r_ed
-            out.append(replace(m, m_read_break=m.m_read_break + shift,
-                               m_left_gp=GenePos(m.m_left_gp.contig, m.m_left_gp.position + shift),
-                               m_right_gp=GenePos(m.m_right_gp.contig, m.m_right_gp.position + shift),
-                               m_left_distance=ld, m_right_distance=rd))
-        self.m_matches = out
+        self.m_matches = [self.shifted(m, *self.best_shift(m)) for m in self.m_matches]
 
     def calc_unique(self) -> None:  # :88-105 (the list is sorted: compare neighbours)
         self.m_unique = 1
@@ -243,16 +251,13 @@ def match_group(m: ReadMatch, n_fusions: int) -> int:
     return n_fusions * m.m_right_gp.contig + m.m_left_gp.contig
 
 
-def cluster_matches(groups: Sequence[Sequence[ReadMatch]], fusions: Sequence[Fusion], fusion_seq: Sequence[str],
-                    settings: Optional[Settings] = None) -> List[FusionResult]:
-    """fusion_mapper.rs:399-486 + sort_fusion_results (:544-556).  ``groups`` = the reference's
-    ``fusion_matches``: one sorted list per (right, left) gene pair, in ``match_group`` order.
-    ``fusion_seq`` = ``Indexer.m_fusion_seq``."""
-    settings = settings or Settings()
-    results: List[FusionResult] = []
+def first_fit_clusters(groups: Sequence[Sequence[ReadMatch]]) -> List[FusionResult]:
+    """The first fit of fusion_mapper.rs:399-420: every match joins the first cluster of its group that supports it,
+    or founds one.  The clusters of all groups, in the order they were made."""
+    out: List[FusionResult] = []
     for fm in groups:
         frs: List[FusionResult] = []
-        for rm in fm:  # first fit
+        for rm in fm:
             for fr in frs:
                 if fr.support(rm):
                     fr.add_match(rm)
@@ -261,32 +266,61 @@ def cluster_matches(groups: Sequence[Sequence[ReadMatch]], fusions: Sequence[Fus
                 fr = FusionResult()
                 fr.add_match(rm)
                 frs.append(fr)
-        for fr in frs:
-            fr.calc_fusion_point()
-            fr.make_reference(fusion_seq[fr.m_left_gp.contig].encode("latin-1"),
-                              fusion_seq[fr.m_right_gp.contig].encode("latin-1"))
-            fr.adjust_fusion_break()
-            fr.calc_unique()
-            fr.update_info(fusions)
-            if not fr.is_qualified(settings):
-                continue
-            if not settings.output_deletions and fr.is_deletion():
-                continue
-            if fr.is_left_protein_forward() != fr.is_right_protein_forward() and not settings.output_untranslated:
-                continue
-            results.append(fr)
+        out += frs
+    return out
+
+
+def adjust_clusters(frs: Sequence[FusionResult]) -> None:
+    for fr in frs:
+        fr.adjust_fusion_break()
+
+
+def cluster_with(groups: Sequence[Sequence[ReadMatch]], fusions: Sequence[Fusion], fusion_seq: Sequence[str],
+                 settings: Optional[Settings], first_fit, adjust) -> List[FusionResult]:
+    """fusion_mapper.rs:399-486 + sort_fusion_results (:544-556), with the two steps that have a bulk form handed in:
+    ``first_fit(groups)`` gives the clusters of all groups in the order they are made, ``adjust(clusters)`` refines the
+    breaks of all their matches.  The clusters do not depend on one another, so running a step for all of them before
+    the next step gives what the reference's cluster-by-cluster loop gives."""
+    settings = settings or Settings()
+    frs = first_fit(groups)
+    for fr in frs:
+        fr.calc_fusion_point()
+        fr.make_reference(fusion_seq[fr.m_left_gp.contig].encode("latin-1"),
+                          fusion_seq[fr.m_right_gp.contig].encode("latin-1"))
+    adjust(frs)
+    results: List[FusionResult] = []
+    for fr in frs:
+        fr.calc_unique()
+        fr.update_info(fusions)
+        if not fr.is_qualified(settings):
+            continue
+        if not settings.output_deletions and fr.is_deletion():
+            continue
+        if fr.is_left_protein_forward() != fr.is_right_protein_forward() and not settings.output_untranslated:
+            continue
+        results.append(fr)
     results.sort(key=lambda fr: (-fr.m_unique, -len(fr.m_matches)))  # stable, like sort_by
     return results
 
 
-def group_and_sort(matches: Sequence[ReadMatch], n_fusions: int) -> List[List[ReadMatch]]:
+def cluster_matches(groups: Sequence[Sequence[ReadMatch]], fusions: Sequence[Fusion], fusion_seq: Sequence[str],
+                    settings: Optional[Settings] = None) -> List[FusionResult]:
+    """fusion_mapper.rs:399-486 + sort_fusion_results (:544-556).  ``groups`` = the reference's
+    ``fusion_matches``: one sorted list per (right, left) gene pair, in ``match_group`` order.
+    ``fusion_seq`` = ``Indexer.m_fusion_seq``."""
+    return cluster_with(groups, fusions, fusion_seq, settings, first_fit_clusters, adjust_clusters)
+
+
+def group_and_sort(matches: Sequence[ReadMatch], n_fusions: int, sort=None) -> List[List[ReadMatch]]:
     """The reference's ``fusion_matches`` after ``sort_matches`` (fusion_mapper.rs:379-384): the
-    non-empty lists only, in index order (empty ones produce nothing in ``cluster_matches``)."""
+    non-empty lists only, in index order (empty ones produce nothing in ``cluster_matches``).  ``sort``: what sorts a
+    list, ``FusionMapper.sort_matches`` unless given."""
     from .fusion_mapper import FusionMapper
+    sort = sort or FusionMapper.sort_matches
     by: dict = {}
     for m in matches:
         by.setdefault(match_group(m, n_fusions), []).append(m)
-    return [FusionMapper.sort_matches(by[k]) for k in sorted(by)]
+    return [sort(by[k]) for k in sorted(by)]
 
 
 def report_text(results: Sequence[FusionResult]) -> str:

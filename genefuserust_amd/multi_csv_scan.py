@@ -221,7 +221,8 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
 def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
-                          hits_cap: int = None, inflate: str = "host") -> List[Tuple[str, List[FusionResult], dict]]:
+                          hits_cap: int = None, inflate: str = "host",
+                          tail: str = "host") -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -243,8 +244,11 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     library's, at least 1024); a CSV with more hits in a chunk is scanned again alone for that chunk.
 
     ``inflate``: where the streamed ``.gz`` files are inflated — the FASTQ files with ``chunk_bytes``, the reference
-    with ``ref_chunk_bytes`` — "host", "auto" or "device": see ``scan.scan_pair_end_files``."""
+    with ``ref_chunk_bytes`` — "host", "auto" or "device": see ``scan.scan_pair_end_files``.  ``tail``: where each
+    CSV's filters, sort, clustering and break refinement run — "host" or "device", see ``scan.scan_pair_end_report``."""
     from .fastq import FastqReader, FastqReaderPair
+    from .report_tail import need_tail
+    need_tail(tail)
     from .fusion_mapper import FusionMapper
     from .indexer import Fusion
     from .scan import (GeneSlices, _route_inflate, finish_matches, open_index, pairs_found, read_contigs,
@@ -267,8 +271,9 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
             produced = (_stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap, fq_inflate)
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
-                kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after)
-                out.append((csv, *report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings)))
+                kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
+                                                tail)
+                out.append((csv, *report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)))
         for name, (_, results, _) in zip(names, out):
             with open(name, "w") as f:
                 f.write(report_json(results, command, version, time, settings))
@@ -290,8 +295,9 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                        lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps))
             else:
                 produced = single_end_found(ix, mapper, *reads)
-            kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:])
-            results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings)
+            kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:],
+                                            tail=tail)
+            results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)
         if names:
             with open(names[k], "w") as f:
                 f.write(report_json(results, command, version, time, settings))
@@ -301,7 +307,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
 def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
-                chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host"):
+                chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host"):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -309,17 +315,17 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     (``scan.scan_pair_end_files``); for a list of CSVs this switch raises ``ValueError`` — multi-CSV mode streams its
     files through ``scan_multi_csv_report(chunk_bytes=...)``, called directly.  ``ref_chunk_bytes`` streams the reference FASTA in every mode (``scan.open_index``,
     ``scan_multi_csv_report``).  ``inflate``: where the streamed ``.gz`` files are inflated, in every mode
-    (``scan.scan_pair_end_files``)."""
+    (``scan.scan_pair_end_files``).  ``tail``: where the report tail runs, in every mode (``scan.scan_pair_end_report``)."""
     from . import scan
     if _rust_stem_ext(fusion_file)[2] == "csv":
         if read2_file:
             results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings,
                                                           chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
-                                                          inflate=inflate)
+                                                          inflate=inflate, tail=tail)
         else:
             results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings,
                                                             chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
-                                                            inflate=inflate)
+                                                            inflate=inflate, tail=tail)
         if json_file:
             with open(json_file, "w") as f:
                 f.write(report_json(results, command, version, time, settings))
@@ -328,4 +334,4 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         raise ValueError("chunk_bytes: this switch keeps the reads of multi-CSV mode resident; call "
                          "scan_multi_csv_report(chunk_bytes=...) to stream them")
     return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
-                                 version, time, ref_chunk_bytes, inflate=inflate)
+                                 version, time, ref_chunk_bytes, inflate=inflate, tail=tail)

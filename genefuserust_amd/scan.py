@@ -102,18 +102,32 @@ def route_counters(count_key: str, n: int, n_found: int, tot: dict = None, chunk
 
 
 def finish_matches(found: List[ReadMatch], mapper, deletion_threshold: int, remove_alignables: bool, before: dict,
-                   after: dict) -> Tuple[List[ReadMatch], dict]:
-    """The tail of every route: the filters, (matches kept in ``sort_matches`` order, counters)."""
-    kept, removed = mapper.filter_matches(found, deletion_threshold)
+                   after: dict, tail: str = "host") -> Tuple[List[ReadMatch], dict]:
+    """The tail of every route: the filters, (matches kept in ``sort_matches`` order, counters).  ``tail``: "host", a
+    library call per match and per comparison; "device", the reasons of all matches in one call on the index's device
+    and the order through ``numpy.lexsort`` (report_tail.py) — the same matches and counters."""
+    from . import report_tail
+    if report_tail.need_tail(tail):
+        kept, removed = report_tail.filter_matches_device(found, deletion_threshold, mapper.m_indexer.info()["device"])
+    else:
+        kept, removed = mapper.filter_matches(found, deletion_threshold)
     if remove_alignables:  # (the reference always does: a whole-genome scan that removes nothing)
         kept, removed["alignables"] = mapper.remove_alignables(kept)
-    return mapper.sort_matches(kept), {**before, **removed, **after}
+    sort = report_tail.order_matches if tail == "device" else mapper.sort_matches
+    return sort(kept), {**before, **removed, **after}
 
 
-def report_matches(kept: List[ReadMatch], counters: dict, fusions, fusion_seq,
-                   settings: Settings) -> Tuple[List[FusionResult], dict]:
-    """Per-gene-pair sort -> cluster -> qualified fusions, most supported first; the counters add ``fusions``."""
-    results = cluster_matches(group_and_sort(kept, len(fusions)), fusions, fusion_seq, settings)
+def report_matches(kept: List[ReadMatch], counters: dict, fusions, fusion_seq, settings: Settings,
+                   tail: str = "host", device: int = -1) -> Tuple[List[FusionResult], dict]:
+    """Per-gene-pair sort -> cluster -> qualified fusions, most supported first; the counters add ``fusions``.
+    ``tail``: "host", ``fusion_result.cluster_matches``; "device", ``report_tail.cluster_matches_device`` on
+    ``device`` — the same results."""
+    from . import report_tail
+    if report_tail.need_tail(tail):
+        results = report_tail.cluster_matches_device(group_and_sort(kept, len(fusions), report_tail.order_matches),
+                                                     fusions, fusion_seq, settings, device)
+    else:
+        results = cluster_matches(group_and_sort(kept, len(fusions)), fusions, fusion_seq, settings)
     counters["fusions"] = len(results)
     return results, counters
 
@@ -190,8 +204,10 @@ def _route_inflate(inflate, chunk_bytes, ref_chunk_bytes):
 
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
-                      chunk_bytes, ref_chunk_bytes=None, inflate="host"):
+                      chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host"):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
+    from .report_tail import need_tail
+    need_tail(tail)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
                          "reference")
@@ -207,14 +223,15 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
             produced = pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
                 ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps))
-        kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:])
+        kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
+                                        tail=tail)
         return kept, counters, fusions, list(ix.m_fusion_seq)
 
 
 def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                         deletion_threshold: int = 50, remove_alignables: bool = False,
                         chunk_bytes: int = None, ref_chunk_bytes: int = None,
-                        inflate: str = "host") -> Tuple[List[ReadMatch], dict]:
+                        inflate: str = "host", tail: str = "host") -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -233,28 +250,36 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     format) goes to the device compressed and is inflated there (bgzf.py); any other file as "host" does.  "device":
     as "auto", but a ``.gz`` file that is not BGZF raises ``ValueError``.  Matches and counters are the same; a member
     that fails raises ``gzip.BadGzipFile``, a file that ends inside a member ``EOFError``, a member that is not BGZF
-    behind the first ``ValueError``."""
+    behind the first ``ValueError``.
+
+    ``tail``: where the filters and the sort behind every route run — "host" (the default), a library call per match
+    and per comparison; "device", all matches at once (report_tail.py: ``gf_rp_filter_device`` on the index's device,
+    the order through ``numpy.lexsort``).  Matches and counters are the same; anything else raises ``ValueError``."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
-                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate)[:2]
+                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                          settings: Settings = None, chunk_bytes: int = None, ref_chunk_bytes: int = None,
-                         inflate: str = "host") -> Tuple[List[FusionResult], dict]:
+                         inflate: str = "host", tail: str = "host") -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` of fusion_result.py turn the list into
     the reference's stdout block and JSON file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``: see
-    ``scan_pair_end_files``."""
+    ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all groups in one host call,
+    the refined breaks of all matches in one ``gf_rp_adjust_device`` call (report_tail.py); the same results,
+    counters and report bytes."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
-                                             settings.deletion_threshold, False, chunk_bytes, ref_chunk_bytes, inflate),
-                          settings)
+                                             settings.deletion_threshold, False, chunk_bytes, ref_chunk_bytes, inflate,
+                                             tail), settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                        ref_chunk_bytes=None, inflate="host"):
+                        ref_chunk_bytes=None, inflate="host", tail="host"):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
+    from .report_tail import need_tail
+    need_tail(tail)
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
     if chunk_bytes is not None and route != "device":
@@ -268,14 +293,14 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
             produced = single_end_found(ix, mapper, *FastqReader(read1_file).read_all_device(ix))
         else:
             produced = _single_end_host_found(mapper, *FastqReader(read1_file).read_all_device(ix))
-        kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:])
+        kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail)
         return kept, counters, fusions, list(ix.m_fusion_seq)
 
 
 def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                           deletion_threshold: int = 50, route: str = "device",
                           chunk_bytes: int = None, ref_chunk_bytes: int = None,
-                          inflate: str = "host") -> Tuple[List[ReadMatch], dict]:
+                          inflate: str = "host", tail: str = "host") -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -287,16 +312,18 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     ``chunk_bytes`` (device route only): None reads the file whole; with a value it is streamed in chunks of that many
     bytes of plain text (scan_stream.scan_single_text_stream), as in ``scan_pair_end_files``; the counters add
     ``chunks``.  ``ref_chunk_bytes`` (either route): the reference FASTA in chunks, see ``scan_pair_end_files``.
-    ``inflate``: where the streamed ``.gz`` files are inflated, see ``scan_pair_end_files``."""
+    ``inflate``: where the streamed ``.gz`` files are inflated, see ``scan_pair_end_files``.  ``tail``: where the
+    filters and the sort run, see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                               ref_chunk_bytes, inflate)[:2]
+                               ref_chunk_bytes, inflate, tail)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                            settings: Settings = None, route: str = "device", chunk_bytes: int = None,
-                           ref_chunk_bytes: int = None, inflate: str = "host") -> Tuple[List[FusionResult], dict]:
+                           ref_chunk_bytes: int = None, inflate: str = "host",
+                           tail: str = "host") -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``: see ``scan_single_end_files``."""
+    ``ref_chunk_bytes``, ``inflate``: see ``scan_single_end_files``; ``tail``: see ``scan_pair_end_report``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
-                                               route, chunk_bytes, ref_chunk_bytes, inflate), settings)
+                                               route, chunk_bytes, ref_chunk_bytes, inflate, tail), settings, tail, device)
