@@ -9,8 +9,8 @@ from .indexer import (Exon, FastaReader, Fusion, Gene, GenePos, Indexer, SeqMatc
                       unpack_matches)
 from .fusion_mapper import FusionMapper, ReadMatch, edit_distance, reverse_complement  # noqa: F401
 from .read_pair import MergedRead, SequenceReadPair, fast_merge_batch, fast_merge_device, scan_pair_end  # noqa: F401
-from .fusion_result import (FusionResult, Settings, cluster_matches, group_and_sort, report_json,  # noqa: F401
-                            report_text)
+from .fusion_result import (FusionResult, Settings, cluster_matches, group_and_sort, report_html,  # noqa: F401
+                            report_json, report_text)
 from .matcher import Matcher, MatcherPanic, remove_alignables  # noqa: F401
 from .fastq import FastqBatch, FastqReader, FastqReaderPair, fastq_cut_device, record_lines  # noqa: F401
 from .multi_csv_scan import (PreparedPairs, prepare_pairs_device, read_csv_list, report_names,  # noqa: F401

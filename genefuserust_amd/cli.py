@@ -1,0 +1,103 @@
+"""The command line: ``python -m genefuserust_amd -1 R1.fq -2 R2.fq -f fusions.csv -r ref.fa``.
+
+The options of the reference (src/argparse.rs) keep their letters and defaults — ``-h`` is the HTML file, help is
+``--help`` only — and the flow is that of src/genefuse.rs: the input files are checked, the command line is printed,
+the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired or single-end), the HTML report and
+the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
+out: the device, the streamed routes, where ``.gz`` files are inflated and where the report tail runs.
+"""
+from __future__ import annotations
+
+import argparse
+import datetime
+import os
+import sys
+import time
+from typing import List, Optional, Sequence
+
+PROG = "genefuserust_amd"
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog=PROG, add_help=False, description="Gene fusion detection from FASTQ files, on an "
+                                "AMD GPU.  The options of GeneFuse keep their letters and defaults.")
+    p.add_argument("--help", action="help", help="show this message and exit (-h is the HTML file)")
+    p.add_argument("-1", "--read1", required=True, help="read1 file name")
+    p.add_argument("-2", "--read2", default="", help="read2 file name")
+    p.add_argument("-f", "--fusion", required=True, help="fusion file name, in CSV format; any other extension: a list "
+                   "of CSV files, one per line, each scanned and reported under its own name")
+    p.add_argument("-r", "--ref", required=True, help="reference fasta file name")
+    p.add_argument("-u", "--unique", type=int, default=2, help="specify the least supporting read number is required "
+                   "to report a fusion, default is 2")
+    p.add_argument("-h", "--html", default="genefuse.html", help="file name to store HTML report, default is "
+                   "genefuse.html; empty: none")
+    p.add_argument("-j", "--json", default="genefuse.json", help="file name to store JSON report, default is "
+                   "genefuse.json; empty: none")
+    p.add_argument("-t", "--thread", type=int, default=4, help="worker thread number (accepted, unused: the scan runs "
+                   "on the device)")
+    p.add_argument("-d", "--deletion", type=int, default=50, help="specify the least deletion length of a intra-gene "
+                   "deletion to report, default is 50")
+    p.add_argument("-D", "--output_deletions", action="store_true", help="long deletions are not output by default, "
+                   "enable this option to output them")
+    p.add_argument("-U", "--output_untranslated_fusions", action="store_true", help="the fusions that cannot be "
+                   "transcribed or translated are not output by default, enable this option to output them")
+    own = p.add_argument_group("this project's own switches")
+    own.add_argument("--device", type=int, default=-1, help="the GPU to run on, default is the current one")
+    own.add_argument("--chunk-bytes", type=int, default=None, help="stream the FASTQ files in chunks of this many bytes "
+                     "of plain text; default: read them whole")
+    own.add_argument("--ref-chunk-bytes", type=int, default=None, help="stream the reference in chunks of this many "
+                     "bytes and cut the gene slices out on the device; default: read it whole on the host")
+    own.add_argument("--inflate", choices=("host", "auto", "device"), default="host", help="where streamed .gz files "
+                     "are inflated: host; auto: BGZF files on the device; device: BGZF files only")
+    own.add_argument("--tail", choices=("host", "device"), default="host", help="where filters, sort, clustering and "
+                     "break refinement run")
+    own.add_argument("--route", choices=("device", "host"), default="device", help="the single-end scan: on the device, "
+                     "or with the records on the host")
+    own.add_argument("--remove-alignables", action="store_true", help="apply the reference's last filter (paired-end, "
+                     "one CSV, whole reference).  Off by default: the reference's Matcher, as it is, removes nothing on "
+                     "a genome and panics on small references")
+    return p
+
+
+def _missing(args) -> Optional[str]:
+    """genefuse.rs:75-84: the first input file that is not there."""
+    for f in (args.ref, args.read1, args.read2, args.fusion):
+        if f and not os.path.isfile(f):
+            return f
+    return None
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = parser().parse_args(argv)
+    missing = _missing(args)
+    if missing is not None:   # (before anything touches the device)
+        print("ERROR: file '%s' doesn't exist, quit now" % missing, file=sys.stderr)
+        return 1
+    from . import __version__
+    from .fusion_result import Settings, report_text
+    from .multi_csv_scan import _rust_stem_ext, scan_multi_csv_report, scan_report
+    command = " ".join([PROG] + argv)
+    started = time.monotonic()
+    print("\n# %s\n" % command)
+    settings = Settings(args.unique, args.deletion, args.output_deletions, args.output_untranslated_fusions)
+    now = str(datetime.datetime.now().astimezone())
+    common = dict(device=args.device, settings=settings, json_file=args.json, html_file=args.html, command=command,
+                  version=__version__, time=now, chunk_bytes=args.chunk_bytes, ref_chunk_bytes=args.ref_chunk_bytes,
+                  inflate=args.inflate, tail=args.tail, originals=bool(args.html))
+    try:
+        if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
+            if args.remove_alignables:
+                raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
+            out = scan_multi_csv_report(args.ref, args.fusion, args.read1, args.read2, **common)   # (streams its files)
+        else:
+            out = scan_report(args.ref, args.fusion, args.read1, args.read2, route=args.route,
+                              remove_alignables=args.remove_alignables, **common)
+    except (ValueError, FileNotFoundError) as e:
+        print("ERROR: %s" % e, file=sys.stderr)
+        return 1
+    per_csv: List = [r for _, r, _ in out] if isinstance(out, list) else [out[0]]
+    for results in per_csv:
+        sys.stdout.write(report_text(results))
+    print("# genefuse v%s, time used: %s seconds\n" % (__version__, time.monotonic() - started))
+    return 0

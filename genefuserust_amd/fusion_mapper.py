@@ -11,7 +11,7 @@ the CPU.  ``scan_single_end`` adds the reverse-complement retry of the scanners
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -44,6 +44,9 @@ class ReadMatch:
     m_source: str = ""    # which read of a pair it was found on: "merged", "r1" or "r2" (scan_pair_end)
     m_quality: bytes = b""  # SequenceRead.m_quality of m_read (reversed when m_read is a reverse complement)
     m_merge_diff: int = -1  # the N of the " merged_diff_N" name suffix when m_read is a merged pair (read.rs:372)
+    # read_match.rs:20, for the HTML report: the FASTQ records the match came from, (name, sequence, strand, quality)
+    # each — both mates of a pair, the one read of single-end input; filled only when a scan is asked for originals
+    m_original_reads: list = field(default_factory=list, compare=False)
 
 
 def edit_distance(a: BytesLike, b: BytesLike) -> int:

@@ -2,7 +2,8 @@
 into fusion candidates, the break-point refinement, qualification and the text / JSON result
 (``FusionMapper::cluster_matches``, src/core/fusion_mapper.rs:399-486 and :544-556;
 ``FusionResult``, src/core/fusion_result.rs:24-511 and :761-798; ``ReadMatch::print``,
-src/core/read_match.rs:153-186; ``JsonReporter::run``, src/core/json_reporter.rs:34-123).
+src/core/read_match.rs:153-186; ``JsonReporter::run``, src/core/json_reporter.rs:34-123; ``HtmlReporter::run``,
+src/core/html_reporter.rs:195-364 with the protein diagram of fusion_result.rs:462-759).
 
 Host logic, as the reference keeps it on the CPU; the only compute is the edit distance, which is
 ``gf_edit_distance`` of libgfmatch.so.  That is one library call per comparison, filter and distance,
@@ -11,12 +12,16 @@ for the 10^5 of a full batch or the thousands of reads a deep panel puts on one 
 ``report_tail.py`` does the same steps in bulk (libgfreport.so); ``cluster_with`` below is the one body
 both share.  Where the
 reference would panic (``subchars`` beyond a string's end) this raises ``IndexError``.
-The HTML report (protein diagrams) is not here.
+``report_html`` writes the HTML report: its ``<body>`` is the reference's byte for byte, the ``<head>`` (script and
+style sheet) is this project's own.  The hidden rows of the supporting reads show ``ReadMatch.m_original_reads``, which
+the scans attach on request (``originals=True``, scan.py).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field, replace
 from typing import List, Optional, Sequence
+
+import numpy as np
 
 from .fusion_mapper import ReadMatch, edit_distance, reverse_complement
 from .indexer import Fusion, Gene, GenePos
@@ -336,9 +341,7 @@ def report_json(results: Sequence[FusionResult], command: str, version: str, tim
                     "\t\"time\":\"%s\",\n" % time, "\t\"fusions\":{"]
     first = True
     for fr in results:
-        if not settings.output_deletions and fr.is_deletion():
-            continue
-        if fr.is_left_protein_forward() != fr.is_right_protein_forward() and not settings.output_untranslated:
+        if _skipped(fr, settings):
             continue
         f.append("\n" if first else ",\n")
         first = False
@@ -372,3 +375,288 @@ def report_json(results: Sequence[FusionResult], command: str, version: str, tim
         f.append("\t\t}")
     f.append("\n\t}\n}\n\n")
     return "".join(f)
+
+
+# ---- the HTML report ------------------------------------------------------------------------------------------------
+
+_F32 = np.float32
+
+
+def _skipped(fr: FusionResult, settings: Settings) -> bool:
+    """What the reporters leave out (html_reporter.rs:263-270, json_reporter.rs): deletions and direction conflicts,
+    unless the settings ask for them."""
+    if not settings.output_deletions and fr.is_deletion():
+        return True
+    return fr.is_left_protein_forward() != fr.is_right_protein_forward() and not settings.output_untranslated
+
+
+def _text(b: bytes) -> str:
+    """Bytes of the input files as text that ``write_report`` turns back into the same bytes."""
+    return b.decode("utf-8", "surrogateescape")
+
+
+def quality_color(q: int) -> str:
+    """read.rs:275-297: the colour of a base by its quality character (a byte value)."""
+    if q >= ord("I"):    # >= Q40
+        return "#78C6B9"
+    if q >= ord("?"):    # Q30 ~ Q39
+        return "#33BBE2"
+    if q >= ord("5"):    # Q20 ~ Q29
+        return "#666666"
+    if q >= ord("0"):    # Q15 ~ Q19
+        return "#E99E5B"
+    return "#FF0000"
+
+
+def _html_seq_with_qual(m: ReadMatch, start: int, length: int) -> str:
+    """read.rs:199-213; a quality string shorter than the read panics there."""
+    out = []
+    for i in range(max(start, 0), min(start + length, len(m.m_read))):
+        if i >= len(m.m_quality):
+            raise IndexError("base %d of a read with %d qualities" % (i, len(m.m_quality)))
+        out.append("<a title='%s'><font color='%s'>%s</font></a>" % (
+            _text(m.m_quality[i:i + 1]), quality_color(m.m_quality[i]), _text(m.m_read[i:i + 1])))
+    return "".join(out)
+
+
+def html_read_row(m: ReadMatch, number: int) -> str:
+    """The cells of a supporting read's row, from ``<td>`` to the last ``</td>`` (html_reporter.rs:338-351,
+    read_match.rs:92-113, read.rs:127-165 with the one break): ``number`` is the row's, from 1."""
+    b = m.m_read_break + 1
+    out = ["<td><a title='%s'>%04d%s</a></span></td><td>%d|%d</td>" % (
+        _text(m.m_name), number, "\u2190" if m.m_reversed else "\u2192", m.m_left_distance, m.m_right_distance)]
+    out.append("<td class='alignright'>%s</td>" % _html_seq_with_qual(m, 0, b))
+    if b > 0:
+        out.append("<td class='alignleft'>%s</td>" % _html_seq_with_qual(m, b, len(m.m_read) - b))
+    return "".join(out)
+
+
+def html_original_reads(m: ReadMatch) -> str:
+    """read_match.rs:115-120 over read.rs:263-272: the four lines of every original record, a newline after each."""
+    return "".join(_text(line) + "\n" for rec in m.m_original_reads for line in rec)
+
+
+def _round_away(x) -> float:
+    """f32::round: half away from zero (Python's ``round`` goes to even)."""
+    x = float(x)
+    if x != x or x in (float("inf"), float("-inf")):
+        return x
+    r = float(int(abs(x) + 0.5))
+    return r if x >= 0 else -r
+
+
+def _as_i32(x) -> int:
+    """Rust's ``as i32`` of a float: towards zero, saturating, NaN is 0."""
+    x = float(x)
+    if x != x:
+        return 0
+    if x >= 2147483647.0:
+        return 2147483647
+    if x <= -2147483648.0:
+        return -2147483648
+    return int(x)
+
+
+def exon_intron_numbers(fr: FusionResult):
+    """fusion_result.rs:462-512 in f32: (left exons, left introns, right exons, right introns) that the diagram draws;
+    halves stand for the exon or intron the break lies in.  A gene without exons underflows ``total_exon - 1`` there."""
+    out = []
+    for gene, is_exon, eid, counts_up in (
+            (fr.m_left_gene, fr.m_left_is_exon, fr.m_left_exon_or_intron_id, fr.is_left_protein_forward()),
+            (fr.m_right_gene, fr.m_right_is_exon, fr.m_right_exon_or_intron_id, not fr.is_right_protein_forward())):
+        total_exon = len(gene.m_exons)
+        if total_exon == 0:
+            raise IndexError("gene %s has no exons" % gene.m_name)
+        total_intron = total_exon - 1
+        if counts_up:    # the part of the gene in front of the break, counted from exon 1
+            exon = _F32(eid) - _F32(0.5) if is_exon else _F32(eid)
+            intron = _F32(eid) - _F32(1.0) if is_exon else _F32(eid) - _F32(0.5)
+        else:            # the part behind it, counted from the last exon
+            exon = _F32(total_exon - eid) + _F32(0.5) if is_exon else _F32(total_exon - eid)
+            intron = _F32(total_intron - eid) + (_F32(1.0) if is_exon else _F32(0.5))
+        out += [exon, intron]
+    return tuple(out)
+
+
+def _exon_intron_td(is_exon: bool, forward: bool, number: int, percent, style: str) -> str:  # :727-759
+    width = _as_i32(percent)
+    if width <= 0:
+        width = 1
+    return "<td class='%s' width='%d%%'>%s</td>" % (
+        style, width, "E%d" % number if is_exon else ("\u2192" if forward else "\u2190"))
+
+
+def html_protein(fr: FusionResult) -> str:
+    """``print_fusion_protein_html`` (fusion_result.rs:514-725): the two genes' exons and introns up to and from the
+    break, as nested tables.  The ``protein_right`` cell carries the left percentage, as in the reference."""
+    le, li, re_, ri = exon_intron_numbers(fr)
+    with np.errstate(all="ignore"):
+        left_size, right_size = le + li, re_ + ri
+        left_percent = _as_i32(_round_away(left_size * _F32(100.0) / (left_size + right_size)))
+        right_percent = 100 - left_percent
+        left_percent, right_percent = left_percent or 1, right_percent or 1
+        out = ["<table width='100%' class='protein_table'>\n<tr>",
+               "<td width='%d%%'>%s</td><td width='%d%%'>%s</td></tr><tr>" % (
+                   left_percent, fr.m_left_gene.m_name, right_percent, fr.m_right_gene.m_name),
+               "<td class='protein_left' width='%d%%'>" % left_percent]
+        # -- the left gene (:579-648): whole steps, the last one a half
+        step_percent = _F32(100.0) / (le + li)
+        half = step_percent * _F32(0.5)
+        forward = fr.is_left_protein_forward()
+        exon, intron, step = 1, 1, 1
+        if not forward:
+            exon = len(fr.m_left_gene.m_exons)
+            intron, step = exon - 1, -1
+        out.append("<table width='100%' class='protein_table'>\n<tr>")
+        done_e = done_i = _F32(0.0)
+        while done_e < le or done_i < li:
+            if done_e < le:
+                out.append(_exon_intron_td(True, forward, exon, half if done_e + _F32(1.0) > le else step_percent,
+                                           "exon_left"))
+                done_e += _F32(1.0)
+                exon += step
+            if done_i < li:
+                out.append(_exon_intron_td(False, forward, intron, half if done_i + _F32(1.0) > li else step_percent,
+                                           "intron_left"))
+                done_i += _F32(1.0)
+                intron += step
+        out.append("</tr></table></td><td class='protein_right' width='%d%%'>" % left_percent)
+        # -- the right gene (:650-725): the first step is the half
+        step_percent = _F32(100.0) / (re_ + ri)
+        half = step_percent * _F32(0.5)
+        forward = fr.is_right_protein_forward()
+        exon = intron = fr.m_right_exon_or_intron_id
+        step = 1 if forward else -1
+        out.append("<table width='100%' class='protein_table'>\n<tr>")
+        done_e = done_i = _F32(0.0)
+        if not fr.m_right_is_exon:
+            out.append(_exon_intron_td(False, forward, intron, half, "intron_right"))
+            done_i += _F32(0.5)
+            intron += step
+            if forward:
+                exon += step
+        while done_e < re_ or done_i < ri:
+            if done_e < re_:
+                first_half = fr.m_right_is_exon and done_e == 0.0
+                out.append(_exon_intron_td(True, forward, exon, half if first_half else step_percent, "exon_right"))
+                done_e += _F32(0.5) if first_half else _F32(1.0)
+                exon += step
+            if done_i < ri:
+                out.append(_exon_intron_td(False, forward, intron, step_percent, "intron_right"))
+                done_i += _F32(1.0)
+                intron += step
+        out.append("</tr></table></td></tr></table>")
+    return "".join(out)
+
+
+def _html_fusion(id_: int, fr: FusionResult) -> str:  # html_reporter.rs:279-364
+    conflict = fr.is_left_protein_forward() != fr.is_right_protein_forward()
+    lr, lx, rr, rx = (_text(x) for x in (fr.m_left_ref, fr.m_left_ref_ext, fr.m_right_ref, fr.m_right_ref_ext))
+    out = ["<div class='fusion_block'><div class='fusion_head'><a name='fusion_id_%d'>%d, %s</a></div>" % (
+               id_, id_, fr.m_title),
+           "<div class='tips'>Inferred protein%s:</div>" % (
+               " (transcription direction conflicts, this fusion may be not transcribed) " if conflict else ""),
+           html_protein(fr),
+           "<div class='tips'>Supporting reads:</div><table><tr class='header'>",
+           "<td class='alignright' colspan='3'>%s = <font color='yellow'>\u2193</font></td>" % fr.m_left_pos,
+           "<td class='alignleft'><font color='yellow'>\u2193</font> = %s</td></tr><tr class='header'>" % fr.m_right_pos,
+           "<td class='alignright' colspan='3'><a title='%s___%s'>%s</a></td>" % (lr, lx, lr),
+           "<td class='alignleft'><a title='%s___%s'>%s</a></td></tr>" % (rx, rr, rr)]
+    for k, m in enumerate(fr.m_matches):
+        row = id_ * 100000 + k
+        out.append("<tr onclick='toggle(%d);'>%s</tr>" % (row, html_read_row(m, k + 1)))
+        out.append("<tr id='%d' style='display:none;'><td colspan='6'><xmp>%s</xmp></td></tr>" % (
+            row, html_original_reads(m)))
+    out.append("</table></div>")
+    return "".join(out)
+
+
+_HTML_HELPER = (
+    "<div id='helper'><p>Helpful tips:</p><ul>"
+    "<li> Base color indicates quality: <font color='#78C6B9'>extremely high (Q40+)</font>, "
+    "<font color='#33BBE2'>high (Q30~Q39) </font>, <font color='#666666'>moderate (Q20~Q29)</font>, "
+    "<font color='#E99E5B'>low (Q15~Q19)</font>, <font color='#FF0000'>extremely low (0~Q14).</font> </li>"
+    "<li> Move mouse over the base, it will show the quality value</li>"
+    "<li> Click on any row, the original read/pair will be displayed</li>"
+    "<li> For pair-end sequencing, GeneFuse tries to merge each pair, with overlapped assigned higher qualities </li>"
+    "</ul><p>Columns:</p><ul>"
+    "<li> col1: is fusion mapped with original read? \u2192 means original read, \u2190 means reverse complement</li>"
+    "<li> col2: edit distance (ed) between read and reference sequence (left_part_ed | right_part_ed)</li>"
+    "<li> col3: read's left part after fusion break</li>"
+    "<li> col4: read's right part after fusion break</li>"
+    "</ul></div>")
+
+# This project's own head: the body needs toggle(id) and the class names below, nothing more.
+_HTML_SCRIPT = (
+    "<script type=\"text/javascript\">\n"
+    "function toggle(id) {\n"
+    "  var row = document.getElementById(id);\n"
+    "  if (row) { row.style.display = (row.style.display === 'table-row') ? 'none' : 'table-row'; }\n"
+    "}\n"
+    "</script>")
+_HTML_STYLE = (
+    "<style type=\"text/css\">\n"
+    "body { margin: 0; }\n"
+    "#container { font-family: Menlo, Consolas, monospace; text-align: center; padding: 4px; }\n"
+    "table { border-collapse: collapse; border: 1px solid #888; }\n"
+    "td { border: 1px solid #ddd; padding: 0 2px; font-size: 10px; }\n"
+    ".alignleft { text-align: left; }\n"
+    ".alignright { text-align: right; }\n"
+    ".software { font-size: 22px; font-weight: bold; padding: 6px; }\n"
+    ".header { background: #111; color: #fff; height: 20px; }\n"
+    "#menu { text-align: left; padding: 10px 0; }\n"
+    "#menu a { color: #0b5cad; font-size: 17px; text-decoration: none; }\n"
+    ".menu_item { text-align: left; padding-top: 4px; }\n"
+    ".fusion_head { text-align: left; color: #0b7fd6; padding: 18px 0 4px 0; }\n"
+    ".fusion_block { margin-bottom: 8px; }\n"
+    ".tips { text-align: left; color: #555; font-size: 10px; padding: 4px; }\n"
+    "#helper { text-align: left; color: #666; font-size: 12px; }\n"
+    "#footer { text-align: left; color: #666; font-size: 10px; padding: 18px 0 0 8px; }\n"
+    ".protein_table { text-align: center; font-size: 8px; }\n"
+    ".protein_left, .protein_right { padding: 0; }\n"
+    ".exon_left { background: #1f3fbf; color: #fff; border: 0; padding: 0; font-size: 8px; }\n"
+    ".exon_right { background: #c22; color: #fff; border: 0; padding: 0; font-size: 8px; }\n"
+    ".intron_left { color: #1f3fbf; padding: 0; font-size: 8px; }\n"
+    ".intron_right { color: #c22; padding: 0; font-size: 8px; }\n"
+    "</style>")
+
+
+def html_body(results: Sequence[FusionResult], command: str, version: str, time: str,
+              settings: Optional[Settings] = None) -> str:
+    """``<body>`` through ``</html>`` as ``HtmlReporter::run`` writes it (html_reporter.rs:72-79, :195-364).  The menu
+    lists every result, numbered over all of them; the blocks leave deletions and direction conflicts out under the
+    settings and number themselves."""
+    settings = settings or Settings()
+    out = ["<body><div id='container'><div class='software'> <a href='https://github.com/OpenGene/GeneFuse' "
+           "style='text-decoration:none;' target='_blank'>GeneFuse</a> <font size='-1'>%s</font></div>" % version,
+           _HTML_HELPER,
+           "<div id='menu'><p>Found %d fusion%s:</p><ul>" % (len(results), "s" if len(results) > 1 else "")]
+    for k, fr in enumerate(results):
+        out.append("<li class='menu_item'><a href='#fusion_id_%d'> %d, %s</a></li>" % (k + 1, k + 1, fr.m_title))
+    out.append("</ul></div>")
+    id_ = 0
+    for fr in results:
+        if _skipped(fr, settings):
+            continue
+        id_ += 1
+        out.append(_html_fusion(id_, fr))
+    out.append("<div id='footer'> <p>%s</p>GeneFuse %s, at %s </div></div></body></html>" % (command, version, time))
+    return "".join(out)
+
+
+def report_html(results: Sequence[FusionResult], command: str, version: str, time: str,
+                settings: Optional[Settings] = None) -> str:
+    """The HTML report, the counterpart of ``report_json``: ``time`` is whatever the caller wants where the reference
+    writes ``Local::now()``.  Byte parity with ``HtmlReporter::run`` is claimed for ``<body>`` .. ``</body>`` only
+    (``html_body``): the ``<title>`` follows the reference's pattern, the script and the style sheet are this
+    project's own.  Bytes of the input files (names, bases, qualities, original records) pass through unescaped, as in
+    the reference; ``write_report`` writes the text as those bytes."""
+    return ("<html><head><meta http-equiv=\"content-type\" content=\"text/html;charset=utf-8\" />"
+            "<title>GeneFuse %s, at %s</title>%s%s</head>" % (version, time, _HTML_SCRIPT, _HTML_STYLE) +
+            html_body(results, command, version, time, settings))
+
+
+def write_report(path: str, text: str) -> None:
+    """A report text to a file, as UTF-8 with the input files' own bytes restored."""
+    with open(path, "w", encoding="utf-8", errors="surrogateescape", newline="") as f:
+        f.write(text)

@@ -23,7 +23,7 @@ from contextlib import ExitStack
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _lib
-from .fusion_result import FusionResult, Settings, report_json
+from .fusion_result import FusionResult, Settings, report_html, report_json, write_report
 from .indexer import Indexer
 from .read_pair import PairScan, companion_scan, gene_reversed_device
 
@@ -157,14 +157,17 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
-def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host"):
+def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host",
+                      originals: bool = False):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
     every index with one hand-back: the cut (the full one: gf_mc_pairs_prepare_device takes the qualities at the bases'
     offsets), pairs prepared once, then per index the scan and the names of its hit records, all queued without a
     synchronisation; ``scan_pack.pack_scans_device`` over the K results; one ``download``.  An index whose scan or
-    names did not fit is scanned again alone for that chunk (``scan_stream._scan_alone``, with room for everything)."""
+    names did not fit is scanned again alone for that chunk (``scan_stream._scan_alone``, with room for everything).
+    ``originals``: the FASTQ records of each index's hit records are gathered behind its scan too and fetched per index,
+    beside the block (whose format stays): a read-back or two more per index and chunk."""
     from . import scan_pack, scan_stream
     from .fusion_mapper import FusionMapper
     from .read_pair import finish_pair_hits
@@ -188,30 +191,35 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
         # (check_lengths: max_read_len is the chunk's longest read, and waiting for a scan's totals is what this avoids)
         steps = [scan_stream._scan_step(ix, texts, batches, m, done, reads, prepared, check_lengths=False)
                  for ix in indexers]
-        scans, gathered = [], []
-        for scan, _, gather in steps:
+        scans, gathered, records = [], [], []
+        for scan, _, gather, gather_records in steps:
             scans.append(scan(**first_caps))
             gathered.append(gather(scans[-1]))
+            if originals:
+                records.append(gather_records(scans[-1]))
         out = []
         for k, u in enumerate(scan_pack.pack_scans_device(scans, gathered).download()):
             if u.bits & ~scan_pack.OVER_NAMES:   # the scan itself did not fit (or is not one): again, alone, with room
                 if u.bits & scan_pack.BAD_SCAN:
                     raise _lib.GfError(_lib.GF_ERR_ARG, "scan %d of a chunk does not hold together: %r" % (k, u.totals))
-                out.append(scan_stream._scan_alone(steps[k], steps[k][1], m, single, True))
-            elif u.bits:   # only its names did not fit: gathered again with the size the header asked for
+                out.append(scan_stream._scan_alone(steps[k], steps[k][1], m, single, True, originals))
+                continue
+            if u.bits:   # only its names did not fit: gathered again with the size the header asked for
                 rec, hb, hq, tot = scans[k].download()
                 tot[count_key] = m
                 out.append((rec, hb, hq, steps[k][2](scans[k], names_cap=u.name_bytes).download(), tot))
             else:
                 out.append((u.rec, u.bases, u.quals, u.names, dict(u.totals, **{count_key: m})))
+            if originals:
+                out[-1] += (scan_stream.fetch_records(records[k], steps[k][3], scans[k]),)
         return out
 
     with ExitStack() as opened:
         sources = scan_stream.open_fastq_sources(opened, files, inflate)
         for per_index in scan_stream._scan_source_stream(indexers[0], sources, chunk_bytes, None, True, scan_records,
                                                          lean=False):
-            for k, (rec, hb, hq, names, tot) in enumerate(per_index):
-                found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names)
+            for k, (rec, hb, hq, names, tot, *orig) in enumerate(per_index):
+                found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names, *orig)
                 for key in sums[k]:
                     sums[k][key] += tot[key]
             chunks += 1
@@ -221,15 +229,18 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
 def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
-                          hits_cap: int = None, inflate: str = "host",
-                          tail: str = "host") -> List[Tuple[str, List[FusionResult], dict]]:
+                          hits_cap: int = None, inflate: str = "host", tail: str = "host", originals: bool = False,
+                          html_file: str = "") -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
     ``read2_file`` the pairs are prepared once, and ``scan.pairs_found`` scans the prepared pairs.  Per CSV:
     parse it, build its index, scan, finish, filter, sort, cluster; the index is closed before the next one.  With
     ``json_file`` each entry's ``report_json`` goes to its ``report_names`` name — two entries with the same stem share
-    a name and the later one overwrites the earlier, as in the reference.  ``ref_chunk_bytes``: None keeps every
+    a name and the later one overwrites the earlier, as in the reference; with ``html_file`` its ``report_html`` goes
+    to the name made of that file in the same way, before the JSON.  ``originals``: the matches carry their FASTQ records
+    for the HTML report (``scan.scan_pair_end_files``); the streamed mode gathers and fetches them per index, beside
+    the one block.  ``ref_chunk_bytes``: None keeps every
     contig of the FASTA on the host for the whole run; with a value one streamed pass over the FASTA cuts the gene
     slices of all CSVs on the device (``ref_cut.cut_gene_slices``), and the results are the same.
 
@@ -256,7 +267,14 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     settings = settings or Settings()
     fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
     csvs = read_csv_list(csv_list_file)
-    names = report_names(json_file, csvs)
+    names, html_names = report_names(json_file, csvs), report_names(html_file, csvs)
+
+    def write(k: int, results) -> None:   # (the HTML first: pescanner.rs:340-342)
+        if html_names:
+            write_report(html_names[k], report_html(results, command, version, time, settings))
+        if names:
+            with open(names[k], "w") as f:
+                f.write(report_json(results, command, version, time, settings))
     if ref_chunk_bytes is None:
         refs = [read_contigs(ref_file)] * len(csvs)
     else:
@@ -268,15 +286,14 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
         with ExitStack() as stack:
             opened = [stack.enter_context(open_index(refs[k], csv, device)) for k, csv in enumerate(csvs)]
             files = (read1_file, read2_file) if read2_file else (read1_file,)
-            produced = (_stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap, fq_inflate)
+            produced = (_stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap, fq_inflate, originals)
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
                                                 tail)
                 out.append((csv, *report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)))
-        for name, (_, results, _) in zip(names, out):
-            with open(name, "w") as f:
-                f.write(report_json(results, command, version, time, settings))
+        for k, (_, results, _) in enumerate(out):
+            write(k, results)
         return out
     reads = prepared = None
     for k, csv in enumerate(csvs):
@@ -292,22 +309,21 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
             mapper = FusionMapper(ix)
             if read2_file:
                 produced = pairs_found(mapper, reads, prepared.max_read_len,
-                                       lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps))
+                                       lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps), originals)
             else:
-                produced = single_end_found(ix, mapper, *reads)
+                produced = single_end_found(ix, mapper, *reads, originals)
             kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:],
                                             tail=tail)
             results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)
-        if names:
-            with open(names[k], "w") as f:
-                f.write(report_json(results, command, version, time, settings))
+        write(k, results)
         out.append((csv, results, counters))
     return out
 
 
 def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
-                chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host"):
+                chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
+                originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -315,17 +331,26 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     (``scan.scan_pair_end_files``); for a list of CSVs this switch raises ``ValueError`` — multi-CSV mode streams its
     files through ``scan_multi_csv_report(chunk_bytes=...)``, called directly.  ``ref_chunk_bytes`` streams the reference FASTA in every mode (``scan.open_index``,
     ``scan_multi_csv_report``).  ``inflate``: where the streamed ``.gz`` files are inflated, in every mode
-    (``scan.scan_pair_end_files``).  ``tail``: where the report tail runs, in every mode (``scan.scan_pair_end_report``)."""
+    (``scan.scan_pair_end_files``).  ``tail``: where the report tail runs, in every mode (``scan.scan_pair_end_report``).
+    ``originals``: the matches carry their FASTQ records, in every mode (``scan.scan_pair_end_files``).  ``html_file``:
+    ``report_html`` goes there, before the JSON, as ``json_file`` does.  ``route``: the single-end scanner's
+    (``scan.scan_single_end_files``).  ``remove_alignables``: the paired-end scanner's (``scan.scan_pair_end_files``);
+    ``ValueError`` in the other modes, which do not have it."""
     from . import scan
+    if remove_alignables and not (_rust_stem_ext(fusion_file)[2] == "csv" and read2_file):
+        raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
     if _rust_stem_ext(fusion_file)[2] == "csv":
         if read2_file:
             results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings,
                                                           chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
-                                                          inflate=inflate, tail=tail)
+                                                          inflate=inflate, tail=tail, originals=originals,
+                                                          remove_alignables=remove_alignables)
         else:
-            results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings,
+            results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings, route,
                                                             chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
-                                                            inflate=inflate, tail=tail)
+                                                            inflate=inflate, tail=tail, originals=originals)
+        if html_file:
+            write_report(html_file, report_html(results, command, version, time, settings))
         if json_file:
             with open(json_file, "w") as f:
                 f.write(report_json(results, command, version, time, settings))
@@ -334,4 +359,5 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         raise ValueError("chunk_bytes: this switch keeps the reads of multi-CSV mode resident; call "
                          "scan_multi_csv_report(chunk_bytes=...) to stream them")
     return scan_multi_csv_report(ref_file, fusion_file, read1_file, read2_file, device, settings, json_file, command,
-                                 version, time, ref_chunk_bytes, inflate=inflate, tail=tail)
+                                 version, time, ref_chunk_bytes, inflate=inflate, tail=tail, originals=originals,
+                                 html_file=html_file)

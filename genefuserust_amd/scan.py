@@ -75,16 +75,26 @@ def match_named(m: ReadMatch, name_of_side) -> ReadMatch:
     return m
 
 
-def named_from_records(hits, l, ltext: bytes, r=None, rtext: bytes = None) -> List[ReadMatch]:
-    """The matches of ``hits`` ((record index, match) pairs) named from the host texts of a whole-file cut."""
+def named_from_records(hits, l, ltext: bytes, r=None, rtext: bytes = None, originals: bool = False) -> List[ReadMatch]:
+    """The matches of ``hits`` ((record index, match) pairs) named from the host texts of a whole-file cut.
+    ``originals``: each also gets its ``m_original_reads``, the FASTQ record of R1 and, for pairs, of R2 — both,
+    whichever read matched (``add_original_pair``, pescanner.rs:456-511; ``add_original_read``, sescanner.rs:191-197)."""
     sides = {"r1": (l, ltext), "r2": (r, rtext)}
+    if originals:
+        for i, m in hits:
+            m.m_original_reads = [record_lines(*sides[side], i) for side in (("r1",) if r is None else ("r1", "r2"))]
     return [match_named(m, lambda side: record_lines(*sides[side], i)[0]) for i, m in hits]
 
 
-def named_from_device(hits, rec, names) -> List[ReadMatch]:
-    """The matches of a streamed chunk named from the names gathered on the device, one per ``gf_pair_hit`` record."""
+def named_from_device(hits, rec, names, originals=None) -> List[ReadMatch]:
+    """The matches of a streamed chunk named from the names gathered on the device, one per ``gf_pair_hit`` record.
+    ``originals``: what ``HitRecords.download`` gave for the same records, each match's ``m_original_reads``."""
     side_of = ("r1", "r1", "r2")   # by the record's source: merged, r1, r2
     name_of = {(int(h["pair_id"]), side_of[int(h["source"])]): nm for h, nm in zip(rec, names)}
+    if originals is not None:
+        records_of = {int(h["pair_id"]): o for h, o in zip(rec, originals)}   # (the same for every record of a pair)
+        for i, m in hits:
+            m.m_original_reads = list(records_of[i])
     return [match_named(m, lambda side: name_of[(i, side)]) for i, m in hits]
 
 
@@ -132,7 +142,8 @@ def report_matches(kept: List[ReadMatch], counters: dict, fusions, fusion_seq, s
     return results, counters
 
 
-def pairs_found(mapper: FusionMapper, reads, max_len: int, scan) -> Tuple[List[ReadMatch], dict, dict]:
+def pairs_found(mapper: FusionMapper, reads, max_len: int, scan,
+                originals: bool = False) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the pairs ``reads`` (``FastqReaderPair.read_all_device``) in push order, and their counters:
     ``scan(**caps)`` is the device scan of those pairs (a ``PairScan``)."""
     (l, ltext), (r, rtext) = reads
@@ -141,11 +152,12 @@ def pairs_found(mapper: FusionMapper, reads, max_len: int, scan) -> Tuple[List[R
     rec, hb, hq, tot = scan_with_room(
         scan, dict(hits_cap=first, bytes_cap=first * 2 * max_len),
         dict(hits_cap=3 * n, bytes_cap=2 * int(l.bases.numel() + r.bases.numel()) + 64, retry_cap=3 * n))[2]
-    found = named_from_records(finish_pair_hits(mapper, rec, hb, hq), l, ltext, r, rtext)
+    found = named_from_records(finish_pair_hits(mapper, rec, hb, hq), l, ltext, r, rtext, originals)
     return (found, *route_counters("pairs", n, len(found), tot))
 
 
-def single_end_found(ix: Indexer, mapper: FusionMapper, b, text: bytes) -> Tuple[List[ReadMatch], dict, dict]:
+def single_end_found(ix: Indexer, mapper: FusionMapper, b, text: bytes,
+                     originals: bool = False) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of a FASTQ batch in HBM, in read order, through one device call, and their counters."""
     from .single_end import scan_single_device
     n = b.n_records
@@ -155,11 +167,12 @@ def single_end_found(ix: Indexer, mapper: FusionMapper, b, text: bytes) -> Tuple
         lambda **caps: scan_single_device(ix, b.bases, b.quals, b.offsets, max_len, **caps),
         dict(hits_cap=first, bytes_cap=first * max_len),
         dict(hits_cap=max(n, 1), bytes_cap=int(b.bases.numel()) + 64, retry_cap=max(n, 1)))[2]
-    found = named_from_records(finish_pair_hits(mapper, rec, hb, hq), b, text)
+    found = named_from_records(finish_pair_hits(mapper, rec, hb, hq), b, text, originals=originals)
     return (found, *route_counters("reads", n, len(found), tot))
 
 
-def _single_end_host_found(mapper: FusionMapper, b, text: bytes) -> Tuple[List[ReadMatch], dict, dict]:
+def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
+                           originals: bool = False) -> Tuple[List[ReadMatch], dict, dict]:
     """The same matches with the records on the host: ``FusionMapper.scan_single_end``, the tail per matched read."""
     off = b.offsets.cpu().numpy()
     bases, quals = b.bases.cpu().numpy().tobytes(), b.quals.cpu().numpy().tobytes()
@@ -171,14 +184,15 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes) -> Tuple[List[R
         m.m_quality = q[::-1] if m.m_reversed else q
         m.m_source = "r1"
         hits.append((i, m))
-    found = named_from_records(hits, b, text)
+    found = named_from_records(hits, b, text, originals=originals)
     return (found, *route_counters("reads", b.n_records, len(found)))
 
 
-def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int,
-                   inflate: str = "host") -> Tuple[List[ReadMatch], dict, dict]:
+def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
+                   originals: bool = False) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
-    order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``."""
+    order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
+    ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``)."""
     from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
     count_key = "pairs" if len(files) == 2 else "reads"
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
@@ -187,8 +201,10 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int,
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        for rec, hb, hq, names, tot in stream(ix, *sources, chunk_bytes, max_read_len=None):
-            found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names)
+        # (originals=False is not passed on: the stream is then called as it always was)
+        for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
+                                                     **({"originals": True} if originals else {})):
+            found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
             chunks += 1
@@ -204,7 +220,7 @@ def _route_inflate(inflate, chunk_bytes, ref_chunk_bytes):
 
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
-                      chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host"):
+                      chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
     from .report_tail import need_tail
     need_tail(tail)
@@ -215,14 +231,14 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
     with open_index(ref_file, fusion_csv, device, ref_chunk_bytes, ref_inflate) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
-            produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate)
+            produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate, originals)
         else:
             reads = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
             (l, _), (r, _) = reads
             max_len = max(l.max_read_len(), r.max_read_len(), 1)
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
             produced = pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
-                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps))
+                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
                                         tail=tail)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -231,7 +247,8 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
 def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                         deletion_threshold: int = 50, remove_alignables: bool = False,
                         chunk_bytes: int = None, ref_chunk_bytes: int = None,
-                        inflate: str = "host", tail: str = "host") -> Tuple[List[ReadMatch], dict]:
+                        inflate: str = "host", tail: str = "host",
+                        originals: bool = False) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -254,29 +271,36 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
 
     ``tail``: where the filters and the sort behind every route run — "host" (the default), a library call per match
     and per comparison; "device", all matches at once (report_tail.py: ``gf_rp_filter_device`` on the index's device,
-    the order through ``numpy.lexsort``).  Matches and counters are the same; anything else raises ``ValueError``."""
+    the order through ``numpy.lexsort``).  Matches and counters are the same; anything else raises ``ValueError``.
+
+    ``originals``: every match also carries ``m_original_reads``, the FASTQ records of both mates of its pair as
+    (name, sequence, strand, quality) — what the HTML report shows under a supporting read.  The whole-file route cuts
+    them from the host text; the streamed route gathers them on the device behind each chunk's scan
+    (``hit_names.hit_records_device``).  The same on every route; without it nothing more is queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
-                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail)[:2]
+                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                          settings: Settings = None, chunk_bytes: int = None, ref_chunk_bytes: int = None,
-                         inflate: str = "host", tail: str = "host") -> Tuple[List[FusionResult], dict]:
+                         inflate: str = "host", tail: str = "host", originals: bool = False,
+                         remove_alignables: bool = False) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
-    supported first.  ``report_text`` / ``report_json`` of fusion_result.py turn the list into
-    the reference's stdout block and JSON file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``: see
-    ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all groups in one host call,
-    the refined breaks of all matches in one ``gf_rp_adjust_device`` call (report_tail.py); the same results,
-    counters and report bytes."""
+    supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
+    the reference's stdout block, JSON file and HTML file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``,
+    ``originals`` (what ``report_html`` shows under the supporting reads), ``remove_alignables`` (the reference's last
+    filter as it is): see ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all
+    groups in one host call, the refined breaks of all matches in one ``gf_rp_adjust_device`` call (report_tail.py);
+    the same results, counters and report bytes."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
-                                             settings.deletion_threshold, False, chunk_bytes, ref_chunk_bytes, inflate,
-                                             tail), settings, tail, device)
+                                             settings.deletion_threshold, remove_alignables, chunk_bytes,
+                                             ref_chunk_bytes, inflate, tail, originals), settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                        ref_chunk_bytes=None, inflate="host", tail="host"):
+                        ref_chunk_bytes=None, inflate="host", tail="host", originals=False):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     from .report_tail import need_tail
     need_tail(tail)
@@ -288,11 +312,11 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
     with open_index(ref_file, fusion_csv, device, ref_chunk_bytes, ref_inflate) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
-            produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate)
+            produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate, originals)
         elif route == "device":
-            produced = single_end_found(ix, mapper, *FastqReader(read1_file).read_all_device(ix))
+            produced = single_end_found(ix, mapper, *FastqReader(read1_file).read_all_device(ix), originals)
         else:
-            produced = _single_end_host_found(mapper, *FastqReader(read1_file).read_all_device(ix))
+            produced = _single_end_host_found(mapper, *FastqReader(read1_file).read_all_device(ix), originals)
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail)
         return kept, counters, fusions, list(ix.m_fusion_seq)
 
@@ -300,7 +324,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
 def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                           deletion_threshold: int = 50, route: str = "device",
                           chunk_bytes: int = None, ref_chunk_bytes: int = None,
-                          inflate: str = "host", tail: str = "host") -> Tuple[List[ReadMatch], dict]:
+                          inflate: str = "host", tail: str = "host",
+                          originals: bool = False) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -313,17 +338,20 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     bytes of plain text (scan_stream.scan_single_text_stream), as in ``scan_pair_end_files``; the counters add
     ``chunks``.  ``ref_chunk_bytes`` (either route): the reference FASTA in chunks, see ``scan_pair_end_files``.
     ``inflate``: where the streamed ``.gz`` files are inflated, see ``scan_pair_end_files``.  ``tail``: where the
-    filters and the sort run, see ``scan_pair_end_files``."""
+    filters and the sort run, see ``scan_pair_end_files``.  ``originals``: every match carries its read's FASTQ
+    record in ``m_original_reads``, on every route; see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                               ref_chunk_bytes, inflate, tail)[:2]
+                               ref_chunk_bytes, inflate, tail, originals)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                            settings: Settings = None, route: str = "device", chunk_bytes: int = None,
                            ref_chunk_bytes: int = None, inflate: str = "host",
-                           tail: str = "host") -> Tuple[List[FusionResult], dict]:
+                           tail: str = "host", originals: bool = False) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``: see ``scan_single_end_files``; ``tail``: see ``scan_pair_end_report``."""
+    ``ref_chunk_bytes``, ``inflate``, ``originals``: see ``scan_single_end_files``; ``tail``: see
+    ``scan_pair_end_report``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
-                                               route, chunk_bytes, ref_chunk_bytes, inflate, tail), settings, tail, device)
+                                               route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals),
+                          settings, tail, device)

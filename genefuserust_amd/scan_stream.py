@@ -6,7 +6,8 @@ list happens on the device, chunk k+1 being read and crossing the link while chu
     byte source (a file, gunzipped as it is read; a text in memory)  --readinto, upload threads-->  pinned staging
     block  --H2D, copy stream-->  device text buffer (behind the carried-over tail of the previous chunk)  -->
     gf_fastq_index_device / gf_fastq_gather_device  -->  gf_scan_pairs_device (merge, map, reverse-complement
-    retries, ordered compaction) or gf_se_scan_device  -->  gf_hn_names_device (the names of the hit records)  -->
+    retries, ordered compaction) or gf_se_scan_device  -->  gf_hn_names_device (the names of the hit records; on
+    request gf_hn_records_device, their whole FASTQ records for the HTML report)  -->
     gf_pair_hit records + their reads + their names, back to the host; gf_pair_hits_finish there.
 
 A chunk ends anywhere; the bytes after its last complete record (of the record count both files
@@ -17,6 +18,7 @@ staging blocks, streams, carries — is ``chunk_stream.ChunkStream``; here is wh
 from __future__ import annotations
 
 from contextlib import closing
+from functools import partial
 from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -65,10 +67,10 @@ def _chunk_reads(batches, m: int, max_read_len: Optional[int]):
 def _scan_step(indexer: Indexer, texts, batches, m: int, done: int, reads, prepared=None, check_lengths: bool = True):
     """How the first ``m`` records of every side (``reads``: what ``_chunk_reads`` gave) are scanned against one index:
     (``scan(**caps)`` -> ``PairScan``, the capacities with room for everything, ``gather(res, **cap)`` -> the
-    ``HitNames`` of a scan's records).  ``prepared``: the ``PreparedPairs`` of these pairs (multi_csv_scan.py), scanned
-    in place of the records themselves."""
+    ``HitNames`` of a scan's records, ``gather_records(res, **cap)`` -> their ``HitRecords``).  ``prepared``: the
+    ``PreparedPairs`` of these pairs (multi_csv_scan.py), scanned in place of the records themselves."""
     from .fastq import fastq_cut_device
-    from .hit_names import hit_names_device
+    from .hit_names import hit_names_device, hit_records_device
     from .single_end import scan_single_device
     single = len(texts) == 1
     offs, nb, mrl = reads
@@ -99,18 +101,37 @@ def _scan_step(indexer: Indexer, texts, batches, m: int, done: int, reads, prepa
                 return scan_pairs_device(indexer, l.bases[:nb[0]], lq, offs[0], r.bases[:nb[1]], rq, offs[1], mrl,
                                          pair_id_base=done, **caps, **qo)
 
+    sides = (texts[0], batches[0]) + (() if single else (texts[1], batches[1]))
+
     def gather(res, **cap):
-        return hit_names_device(indexer, res, texts[0], batches[0], *(() if single else (texts[1], batches[1])),
-                                pair_id_base=done, **cap)
-    return scan, room, gather
+        return hit_names_device(indexer, res, *sides, pair_id_base=done, **cap)
+
+    def gather_records(res, **cap):
+        return hit_records_device(indexer, res, *sides, pair_id_base=done, **cap)
+    return scan, room, gather, gather_records
 
 
-def _scan_alone(step, first_caps: dict, m: int, single: bool, names: bool):
+def fetch_records(recs, gather_records, res):
+    """What a ``HitRecords`` downloads; records of more bytes than it had room for are gathered once more, with the
+    room the first call asked for."""
+    _, need, over, _ = (int(x) for x in recs.totals.cpu())
+    if over:
+        recs = gather_records(res, records_cap=need)
+    return recs.download()
+
+
+def _scan_alone(step, first_caps: dict, m: int, single: bool, names: bool, originals: bool = False):
     """One index's scan of a chunk with a read-back of its own (``scan_with_room``: ``first_caps``, then the room), the
-    names of the hit records gathered behind the scan: (records, hit bases, hit qualities, names or None, totals)."""
-    scan, room, gather = step
+    names of the hit records gathered behind the scan: (records, hit bases, hit qualities, names or None, totals); with
+    ``originals`` their FASTQ records are gathered too, and follow as a sixth element."""
+    scan, room, gather, gather_records = step
     # (the names are queued behind the scan: the record count stays on the device)
-    res, nm, out = scan_with_room(scan, first_caps, room, gather if names else None)
+    behind = None
+    if names or originals:
+        def behind(res):
+            return (gather(res) if names else None, gather_records(res) if originals else None)
+    res, gathered, out = scan_with_room(scan, first_caps, room, behind)
+    nm, recs = gathered or (None, None)
     name_list = None
     if names:
         _, need, over, _ = (int(x) for x in nm.totals.cpu())
@@ -118,14 +139,17 @@ def _scan_alone(step, first_caps: dict, m: int, single: bool, names: bool):
             nm = gather(res, names_cap=need)
         name_list = nm.download()
     out[3]["reads" if single else "pairs"] = m
-    return out[0], out[1], out[2], name_list, out[3]
+    chunk = (out[0], out[1], out[2], name_list, out[3])
+    return chunk + (fetch_records(recs, gather_records, res),) if originals else chunk
 
 
-def _scan_records(indexer: Indexer, texts, batches, m: int, done: int, max_read_len: Optional[int], names: bool):
+def _scan_records(indexer: Indexer, texts, batches, m: int, done: int, max_read_len: Optional[int], names: bool,
+                  originals: bool = False):
     """The first ``m`` records of every side scanned — first with the library's default capacities — and the names of
-    the hit records: (records, hit bases, hit qualities, names or None, totals)."""
+    the hit records: (records, hit bases, hit qualities, names or None, totals), with ``originals`` the records' FASTQ
+    records behind them."""
     step = _scan_step(indexer, texts, batches, m, done, _chunk_reads(batches, m, max_read_len))
-    return _scan_alone(step, {}, m, len(texts) == 1, names)
+    return _scan_alone(step, {}, m, len(texts) == 1, names, originals)
 
 
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
@@ -184,16 +208,19 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 
 
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
-                            max_read_len: Optional[int] = 320,
-                            names: bool = True) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            max_read_len: Optional[int] = 320, names: bool = True,
+                            originals: bool = False) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
     the records' reads (``hit_names_device``; None with ``names=False``), totals); ``totals["pairs"]`` is the chunk's
     pair count.  Records pair up by position; the shorter file ends both (fastq_reader.rs:209-218).  The next chunk of
     each source is read (gunzipped) and uploaded on host threads while the device works on the current one; the host
-    holds two staging blocks of ``chunk_bytes`` per side.  ``max_read_len=None``: the longest read of each chunk."""
-    return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names)
+    holds two staging blocks of ``chunk_bytes`` per side.  ``max_read_len=None``: the longest read of each chunk.
+    ``originals``: a sixth element per chunk, the FASTQ records of the hit records' pairs (``hit_records_device``: per
+    record the (name, sequence, strand, quality) of R1 and of R2), gathered behind the scan before the chunk goes."""
+    return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names,
+                               partial(_scan_records, originals=True) if originals else _scan_records)
 
 
 def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
@@ -208,14 +235,17 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
-                            names: bool = True) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            names: bool = True,
+                            originals: bool = False) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
-    trailing newline counts (fastq_reader.rs:75-147)."""
+    trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
+    per hit record."""
     if isinstance(source, np.ndarray):
         source = ArraySource(source)
-    return _scan_source_stream(indexer, (source,), chunk_bytes, max_read_len, names)
+    return _scan_source_stream(indexer, (source,), chunk_bytes, max_read_len, names,
+                               partial(_scan_records, originals=True) if originals else _scan_records)
 
 
 def scan_pair_end_text(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,

@@ -9,6 +9,11 @@ parity flag.  Also, with HIP events around single calls on one chunk of that tex
 pair scan it follows, and the single-end chunk's FASTQ cut with and without the copy of the quality lines next to its
 scan.  Result (medians and ranges) to ``--out``.
 
+``--originals`` instead runs the streamed pair scan of the plain files, at the last ``--chunk-mb`` size, once without
+and once with ``originals=True`` (the FASTQ records of the hit records gathered behind every chunk's scan,
+``hit_records_device``) and writes both times, the bytes gathered and the commit to
+``profiles/hit_records_bench.json``: a number to have, not one that is asserted.
+
 The parent process never opens the GPU: every step is a child process of this file under its own ``timeout``, and the
 first one that fails ends the run."""
 import argparse
@@ -161,6 +166,49 @@ def step_chunk(a):
     ix.close()
 
 
+def step_originals(a):
+    """The streamed pair scan without and with the originals, once each (after a warm run)."""
+    import torch
+    from genefuserust_amd import hit_names
+    from genefuserust_amd.scan import scan_pair_end_files
+    p = _paths(a.dir)
+    chunk_bytes = a.chunk_mb[-1] << 20
+    gathered = []
+    gather = hit_names.hit_records_device
+
+    def counting(*args, **kwargs):   # (the totals stay on the device until the runs are over)
+        gathered.append(gather(*args, **kwargs))
+        return gathered[-1]
+    hit_names.hit_records_device = counting
+
+    def run(originals):
+        t0 = time.perf_counter()
+        out = scan_pair_end_files(p["fa"], p["csv"], p["r1"], p["r2"], chunk_bytes=chunk_bytes, originals=originals)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+    run(True)   # warm: the first call of a process loads the code objects
+    del gathered[:]
+    t_without, without = run(False)
+    assert not gathered
+    t_with, with_ = run(True)
+    totals = [[int(x) for x in g.totals.cpu()] for g in gathered]
+    print(json.dumps({"chunk_bytes": chunk_bytes, "chunks": with_[1]["chunks"], "without_originals_s": round(t_without, 3),
+                      "with_originals_s": round(t_with, 3), "gather_calls": len(totals),
+                      "spans_gathered": sum(t[0] for t in totals), "bytes_gathered": sum(t[1] for t in totals),
+                      "matches_kept": len(with_[0]), "parity": without[0] == with_[0] and without[1] == with_[1],
+                      "counters": with_[1]}))
+
+
+def commit():
+    head = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True)
+    if head.returncode == 0:
+        return head.stdout.strip()
+    try:   # (a snapshot without .git: tools/stamp_head.sh wrote the commit before it was taken)
+        return json.load(open(os.path.join(ROOT, ".git_head"))).get("git_head")
+    except (OSError, ValueError):
+        return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=1_000_000)
@@ -169,21 +217,31 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--chunk-mb", type=int, nargs="+", default=[16, 64])
     ap.add_argument("--step-timeout", type=int, default=420, help="seconds a step may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_files_bench.json"))
-    ap.add_argument("--step", choices=["files", "routes", "chunk"], help="(internal) run one step in this process")
+    ap.add_argument("--out", help="default: profiles/stream_files_bench.json, with --originals "
+                    "profiles/hit_records_bench.json")
+    ap.add_argument("--originals", action="store_true", help="measure the streamed pair scan with and without the "
+                    "gather of the original records, and nothing else")
+    ap.add_argument("--step", choices=["files", "routes", "chunk", "originals"],
+                    help="(internal) run one step in this process")
     ap.add_argument("--dir")
     ap.add_argument("--layout", choices=["paired", "single"])
     ap.add_argument("--zipped", type=int, default=0)
     a = ap.parse_args()
     if a.step:
-        {"files": step_files, "routes": step_routes, "chunk": step_chunk}[a.step](a)
+        {"files": step_files, "routes": step_routes, "chunk": step_chunk, "originals": step_originals}[a.step](a)
         return
+    out = a.out or os.path.join(ROOT, "profiles", "hit_records_bench.json" if a.originals else "stream_files_bench.json")
     common = ["--pairs", str(a.pairs), "--read-len", str(a.read_len), "--shape", a.shape, "--runs", str(a.runs),
               "--chunk-mb"] + [str(x) for x in a.chunk_mb]
-    result = {"tool": "tools/bench_stream_files.py", "runs_each": a.runs, "order": "alternating", "routes": []}
+    if a.originals:
+        result = {"tool": "tools/bench_stream_files.py --originals", "commit": commit(), "runs_each": 1}
+    else:
+        result = {"tool": "tools/bench_stream_files.py", "runs_each": a.runs, "order": "alternating", "routes": []}
     with tempfile.TemporaryDirectory() as d:
         steps = [("files", [])] + [("routes", ["--layout", lay, "--zipped", str(z)])
                                    for lay in ("paired", "single") for z in (0, 1)] + [("chunk", [])]
+        if a.originals:
+            steps = [("files", []), ("originals", [])]
         for name, extra in steps:
             cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--step", name,
                    "--dir", d] + common + extra
@@ -197,9 +255,11 @@ def main():
                 result["input"] = line
             elif name == "routes":
                 result["routes"].append(line)
+            elif name == "originals":
+                result["streamed_pair_scan"] = line
             else:
                 result["chunk_calls"] = line
-    with open(a.out, "w") as f:
+    with open(out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
 
