@@ -53,12 +53,12 @@ __device__ __forceinline__ uint32_t gf_spread16(uint32_t x) {
 }
 
 // every 4th bit (bits 0,4,..,28) of x gathered into the low 8 bits
+// (r05: two bits a byte, then one dot product of the four bytes with (1, 4, 16, 64) puts byte b's pair at bits 2b, 2b+1 —
+//  four instructions where two more rounds of shift, or and mask made it nine; it runs for every word verified)
 __device__ __forceinline__ uint32_t gf_gather_nibble_lsb(uint32_t x) {
   x &= 0x11111111u;
   x = (x | (x >> 3)) & 0x03030303u;
-  x = (x | (x >> 6)) & 0x000F000Fu;
-  x = (x | (x >> 12)) & 0xFFu;
-  return x;
+  return __builtin_amdgcn_udot4(x, 0x40100401u, 0u, false);
 }
 
 // wave-aggregated append: returns this lane's slot when `want`, one atomic per wave
@@ -186,6 +186,23 @@ __device__ __forceinline__ uint32_t gf_clean16(uint32_t z_lo, uint32_t z_hi) {
     hi &= hi >> sh;
   }
   return lo;
+}
+
+// gf_clean16 for a read's words taken from the last to the first (r05).  gf_clean16 runs two chains of and-with-shifted-
+// self: one over the word and its successor, one over the successor alone, which only feeds the first its low bits —
+// the runs of 1, 2, 4 and 8 good bases that start in the successor's first bases and end inside it.  Those are the very
+// values the successor's own first chain went through when it was the word.  So, going backwards, a word's four
+// intermediate values are kept (n[0..3], all zero behind the last word: nothing good there) and the next word down uses
+// them: 9 instructions a word instead of 16.  z = the word's bad-base flags at the even bits.
+__device__ __forceinline__ uint32_t gf_clean16_chain(uint32_t z, uint32_t (&n)[4]) {
+  uint32_t l = ~z & 0x55555555u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t t = l & __builtin_amdgcn_alignbit(n[k], l, 2u << k);
+    n[k] = l;
+    l = t;
+  }
+  return l;
 }
 
 // 16 ASCII bases -> 32 code bits and 16 "not A/C/G/T" bits.  The expected letter of each
@@ -368,23 +385,15 @@ __device__ __forceinline__ void gf_verify_words2(const GfTable& T, const uint32_
   uint2 gw[PW + 1];
 #pragma unroll
   for (int j = 0; j < PW + 1; ++j) gw[j] = gp[j];
-  uint32_t zz_cur;
-  {
-    const uint32_t x = pk[0] ^ __builtin_amdgcn_alignbit(gw[1].x, gw[0].x, bo);
-    zz_cur = (x | (x >> 1)) & 0x55555555u;
-  }
+  uint32_t run[4] = {0, 0, 0, 0};  // (gf_clean16_chain: from the last word to the first)
 #pragma unroll
-  for (int j = 0; j < PW; ++j) {
-    uint32_t zz_next = 0x55555555u;
-    if (j + 1 < PW) {
-      const uint32_t x = pk[j + 1] ^ __builtin_amdgcn_alignbit(gw[j + 2 <= PW ? j + 2 : PW].x, gw[j + 1].x, bo);
-      zz_next = (x | (x >> 1)) & 0x55555555u;
-    }
+  for (int j = PW - 1; j >= 0; --j) {
+    const uint32_t x = pk[j] ^ __builtin_amdgcn_alignbit(gw[j + 1].x, gw[j].x, bo);
+    const uint32_t zz = (x | (x >> 1)) & 0x55555555u;  // mismatching base
     const uint32_t u = __builtin_amdgcn_alignbit(gw[j + 1].y, gw[j].y, bo);
-    const uint32_t clean = gf_clean16(zz_cur, zz_next);
+    const uint32_t clean = gf_clean16_chain(zz, run);
     vmb[j >> 2] |= gf_gather_nibble_lsb(clean & u & 0x11111111u) << (8 * (j & 3));
     hmb[j >> 2] |= gf_gather_nibble_lsb(clean & (u >> 1) & 0x11111111u) << (8 * (j & 3));
-    zz_cur = zz_next;
   }
 }
 
@@ -576,6 +585,18 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
 #pragma unroll
       for (int k = 0; k < NT; ++k) e_todo[k] = 0;
       uint32_t w0 = 0, sh = 0;
+      // r05: the 10-word form cuts a read's packed words out of the tile ONCE (PW + 1 LDS reads, where the read's place in
+      // the tile is known) and keeps them — the seeds, the verification, the queue record and the list entry each cut
+      // them again, two LDS reads and a funnel shift a word, up to 34 cuts for a tile; the kernel had the registers
+      // (89 of the 128 that four waves per SIMD allow).  The longer forms, which have not, cut where they need a word.
+      constexpr bool HOLD = PW == 10;
+      uint32_t pk_held[HOLD ? PW : 1];
+#pragma unroll
+      for (int j = 0; j < (HOLD ? PW : 1); ++j) pk_held[j] = 0;
+      auto pk_word = [&](int j) -> uint32_t {
+        if constexpr (HOLD) return pk_held[j];
+        else return gf_cut_pk(s_pk, w0, sh, j);
+      };
 #if defined(GF_ABLATE_SV) && GF_ABLATE_SV == 6  // timing only: staging and conversion, one LDS word per read
       if (in_range) counts[r] = s_pk[((uint32_t)(off0 - base_off) + mis) >> 4] == 0x1234567u ? 1 : 0;
       if (false) {
@@ -597,6 +618,15 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
           const uint32_t pos = (uint32_t)(off0 - base_off) + mis;
           w0 = pos >> 4;
           sh = 2u * (pos & 15u);
+          if constexpr (HOLD) {
+            uint32_t lo = s_pk[w0];
+#pragma unroll
+            for (int j = 0; j < PW; ++j) {
+              const uint32_t hi = s_pk[w0 + j + 1];
+              pk_held[j] = __builtin_amdgcn_alignbit(hi, lo, sh);
+              lo = hi;
+            }
+          }
           // does the read hold any base outside A/C/G/T?  (flag bits pos .. pos+L-1)
           uint32_t anybad = 0;
           {
@@ -619,7 +649,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
           uint32_t key[4];
           uint32_t okm = 0;
 #pragma unroll
-          for (int s = 0; s < 4; ++s) key[s] = 2 * s < PW ? gf_cut_pk(s_pk, w0, sh, 2 * s) : 0u;
+          for (int s = 0; s < 4; ++s) key[s] = 2 * s < PW ? pk_word(2 * s) : 0u;
           if (!anybad) {
             nvalid = (L - GF_KMER) / 2 + 1;
 #pragma unroll
@@ -800,10 +830,10 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
 #pragma unroll 1
             for (uint32_t rnd = 0; rnd < 2; ++rnd) {
               if (alive) {
-                uint32_t wlo = gf_cut_pk(s_pk, w0, sh, 0);
+                uint32_t wlo = pk_word(0);
 #pragma unroll
                 for (int j = 0; j < PW; ++j) {
-                  const uint32_t whi = j + 1 < PW ? gf_cut_pk(s_pk, w0, sh, j + 1) : 0u;
+                  const uint32_t whi = j + 1 < PW ? pk_word(j + 1) : 0u;
                   const uint32_t byte = (pp[j >> 2] >> (8 * (j & 3))) & 0xFFu;  // this word's 8 windows
                   uint32_t word[2], bits[2];
 #pragma unroll
@@ -842,10 +872,10 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
           if (K == GF_NONE_LIN && T.bloom_in_l2 == 2) {
             filt_done = true;
             int npos = 0, rem = nvalid;
-            uint32_t wlo = gf_cut_pk(s_pk, w0, sh, 0);
+            uint32_t wlo = pk_word(0);
 #pragma unroll
             for (int j = 0; j < PW; ++j) {
-              const uint32_t whi = j + 1 < PW ? gf_cut_pk(s_pk, w0, sh, j + 1) : 0u;
+              const uint32_t whi = j + 1 < PW ? pk_word(j + 1) : 0u;
 #ifndef GF_FILTER_OLD
               // (r02 e: the kernel's vector ALUs are busy 78 % of the time and this loop is half of their
               //  instructions.  The four answers of a word are gathered as fail bits on the even positions of one
@@ -926,26 +956,16 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
             uint2 gw[PW + 1];
 #pragma unroll
             for (int j = 0; j < PW + 1; ++j) gw[j] = gp[j];
-            uint32_t zz_cur;
-            {
-              const uint32_t x = gf_cut_pk(s_pk, w0, sh, 0) ^ __builtin_amdgcn_alignbit(gw[1].x, gw[0].x, bo);
-              zz_cur = (x | (x >> 1)) & 0x55555555u;  // mismatching base
-              if (anybad) zz_cur |= gf_cut_iv(s_iv, pos, L, 0);
-            }
+            uint32_t run[4] = {0, 0, 0, 0};  // (gf_clean16_chain: from the last word to the first)
 #pragma unroll
-            for (int j = 0; j < PW; ++j) {
-              uint32_t zz_next = 0x55555555u;
-              if (j + 1 < PW) {
-                const uint32_t x = gf_cut_pk(s_pk, w0, sh, j + 1) ^
-                                   __builtin_amdgcn_alignbit(gw[j + 2 <= PW ? j + 2 : PW].x, gw[j + 1].x, bo);
-                zz_next = (x | (x >> 1)) & 0x55555555u;
-                if (anybad) zz_next |= gf_cut_iv(s_iv, pos, L, j + 1);
-              }
+            for (int j = PW - 1; j >= 0; --j) {
+              const uint32_t x = pk_word(j) ^ __builtin_amdgcn_alignbit(gw[j + 1].x, gw[j].x, bo);
+              uint32_t zz = (x | (x >> 1)) & 0x55555555u;  // mismatching base
+              if (anybad) zz |= gf_cut_iv(s_iv, pos, L, j);
               const uint32_t u = __builtin_amdgcn_alignbit(gw[j + 1].y, gw[j].y, bo);
-              const uint32_t ver = gf_clean16(zz_cur, zz_next) & u & 0x11111111u;
+              const uint32_t ver = gf_clean16_chain(zz, run) & u & 0x11111111u;
               vmb[j >> 2] |= gf_gather_nibble_lsb(ver) << (8 * (j & 3));
-              zz_cur = zz_next;
-              if (j & 1) __builtin_amdgcn_sched_barrier(0);  // keep it a stream: two words in flight
+              if (!(j & 1)) __builtin_amdgcn_sched_barrier(0);  // keep it a stream: two words in flight
             }
           }
           int v1 = 0;
@@ -1006,7 +1026,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
 #pragma unroll
             for (int k = 0; k < NT; ++k) ew[2 + k] = pp_q[k];
 #pragma unroll
-            for (int j = 0; j < PW; ++j) ew[2 + NT + j] = gf_cut_pk(s_pk, w0, sh, j);
+            for (int j = 0; j < PW; ++j) ew[2 + NT + j] = pk_word(j);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               gf_u32x4 q;
@@ -1029,7 +1049,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
         if (undecided) {
           uint32_t pkw[PW + 1];
 #pragma unroll
-          for (int j = 0; j < PW; ++j) pkw[j] = gf_cut_pk(s_pk, w0, sh, j);
+          for (int j = 0; j < PW; ++j) pkw[j] = pk_word(j);
           pkw[PW] = 0;
           gf_entry_store<PW>(my_list + slot_b, (uint32_t)r, e_v1v2, e_todo, pkw);
         }
@@ -1053,7 +1073,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
 #pragma unroll
           for (int k = 0; k < NT; ++k) ew[2 + k] = e_todo[k];
 #pragma unroll
-          for (int j = 0; j < PW; ++j) ew[2 + NT + j] = gf_cut_pk(s_pk, w0, sh, j);
+          for (int j = 0; j < PW; ++j) ew[2 + NT + j] = pk_word(j);
         }
         uint4* s_ent = (uint4*)s_pk;
         for (int c0 = 0; c0 < cnt; c0 += CH) {
