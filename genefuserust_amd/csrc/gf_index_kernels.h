@@ -13,10 +13,7 @@
 // dupes(start in dupes[]) / HIGH, statistics), the side list into the duplicate lists (each sorted by the thread
 // that brings its last site); the same pass over the side list flags every site of a HIGH key (the odd bit beside its
 // "unique" flag in gdu) and leaves the smallest of them in the key's slot (r04: what the mapping kernels prove "cannot
-// vote" from).  The first form is kept behind GF_BUILD_TWO_PASS (experiments; it keeps neither):
-//   COUNT   insert keys with 64-bit CAS, count occurrences
-//   classify (count -> unique / dupes(start in dupes[]) / HIGH)
-//   FILL    write site codes
+// vote" from).
 // Slot placement inside a bucket depends on the race order of different keys, so
 // the table's byte image is not reproducible run to run; every lookup result is.
 #pragma once
@@ -36,33 +33,8 @@ struct GfGenes {
   int32_t n_genes;
 };
 
-enum { GF_MODE_COUNT = 0, GF_MODE_FILL = 1 };
-
 // indexer.rs:159: the gene slices are upper-cased before they are indexed (ASCII letters; the FASTA reader keeps
-// letters, '-' and '*' only).  In place on the device copy, 16 bytes per thread and step.
-__global__ __launch_bounds__(256) void gf_k_upper_inplace(uint8_t* __restrict__ p, unsigned long long n_vec) {
-  uint4* v = (uint4*)p;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n_vec; i += (unsigned long long)gridDim.x * 256) {
-    uint4 q = v[i];
-    uint32_t w[4] = {q.x, q.y, q.z, q.w};
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      uint32_t x = w[k], y = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        uint32_t ch = (x >> (8 * b)) & 0xFFu;
-        if (ch - 'a' < 26u) ch -= 32u;
-        y |= ch << (8 * b);
-      }
-      any |= y != x;
-      w[k] = y;
-    }
-    if (any) v[i] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
-// The same out of place, `src` being the host's pinned staging block: the kernel pulls a chunk of the gene bytes
+// letters, '-' and '*' only).  Out of place, `src` being the host's pinned staging block: the kernel pulls a chunk of the gene bytes
 // over the bus itself as soon as the host has gathered it (r03: a DMA per megabyte cost 40 us of set-up each, a
 // launch of this costs 5).
 __global__ __launch_bounds__(256) void gf_k_upper_copy(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
@@ -92,49 +64,6 @@ __device__ __forceinline__ uint64_t gf_atomic_load64(uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// COUNT pass: claim a slot for `key` (or find it) and bump its occurrence count.
-// A bucket's slots are claimed in order (a slot is taken only by a thread that saw every slot before it
-// occupied), so the occupied slots are a prefix.  The eight slots are read at once — one round trip to the
-// bucket's 64-byte line in place of one per occupied slot — and the slot-by-slot search starts at the first
-// slot that was still empty in that snapshot; keys never change or leave, so a key seen there is there.
-__device__ __forceinline__ void gf_insert_count(uint64_t* slots, uint32_t nbuckets, uint32_t key) {
-  uint32_t b = gf_bucket_of(key, nbuckets);
-  for (uint32_t guard = 0; guard <= nbuckets; ++guard) {
-    uint64_t* bucket = slots + (size_t)b * GF_SLOTS_PER_BUCKET;
-    // (plain loads: a stale line shows an earlier state of the bucket — fewer slots taken, never a wrong key —
-    //  and the CAS below finds out what a slot holds by now)
-    const uint4* q = (const uint4*)bucket;
-    const uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-    const uint32_t lo[8] = {q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, q3.x, q3.z};
-    const uint32_t hi[8] = {q0.y, q0.w, q1.y, q1.w, q2.y, q2.w, q3.y, q3.w};
-    int hit = -1, first_empty = GF_SLOTS_PER_BUCKET;
-#pragma unroll
-    for (int j = GF_SLOTS_PER_BUCKET - 1; j >= 0; --j) {
-      if ((lo[j] & GF_VAL_LOW) == 0) first_empty = j;
-      else if (hi[j] == key) hit = j;
-    }
-    if (hit >= 0) {
-      atomicAdd((unsigned int*)(bucket + hit), 1u);  // low word = count
-      return;
-    }
-    for (int j = first_empty; j < GF_SLOTS_PER_BUCKET; ++j) {
-      uint64_t cur = j == first_empty ? 0ull : gf_atomic_load64(bucket + j);
-      if ((cur & GF_VAL_LOW) == 0) {
-        uint64_t want = ((uint64_t)key << 32) | 1ull;
-        uint64_t prev = atomicCAS((unsigned long long*)(bucket + j), 0ull, (unsigned long long)want);
-        if (prev == 0) return;
-        cur = prev;
-      }
-      if ((uint32_t)(cur >> 32) == key) {
-        atomicAdd((unsigned int*)(bucket + j), 1u);
-        return;
-      }
-    }
-    atomicOr((unsigned int*)bucket, GF_VAL_OVF);  // slot 0, low word
-    b = (b + 1 == nbuckets) ? 0 : b + 1;
-  }
-}
-
 // Slot holding `key` (must have been inserted; the table no longer changes its keys).
 __device__ __forceinline__ uint64_t* gf_find_slot(uint64_t* slots, uint32_t nbuckets, uint32_t key) {
   uint32_t b = gf_bucket_of(key, nbuckets);
@@ -153,27 +82,6 @@ __device__ __forceinline__ uint64_t* gf_find_slot(uint64_t* slots, uint32_t nbuc
     b = (b + 1 == nbuckets) ? 0 : b + 1;
   }
   return nullptr;
-}
-
-// FILL pass: store the site code of one occurrence; true when the key has exactly this one site (the
-// caller then sets the site's "unique" flag in gdu, a wavefront's flags at a time).
-__device__ __forceinline__ bool gf_fill_site(uint64_t* slots, uint32_t nbuckets, uint32_t* dupes, uint32_t key, uint32_t lin) {
-  uint64_t* s = gf_find_slot(slots, nbuckets, key);
-  if (!s) return false;
-  uint32_t* valp = (uint32_t*)s;  // little-endian: low word = val
-  uint32_t val = *valp;
-  uint32_t type = (val & GF_VAL_LOW) >> GF_TYPE_SHIFT;
-  if (type == GF_TYPE_UNIQUE) {
-    // exactly one occurrence => exactly one writer
-    *valp = (val & GF_VAL_OVF) | (GF_TYPE_UNIQUE << GF_TYPE_SHIFT) | (lin & GF_LIN_MASK);
-    return true;
-  } else if (type == GF_TYPE_DUPES) {
-    uint32_t cnt = (val >> GF_DUPE_COUNT_SHIFT) & 7u;
-    uint32_t start = val & GF_DUPE_START_MASK;
-    for (uint32_t k = 0; k < cnt; ++k)
-      if (atomicCAS(dupes + start + k, GF_DUPE_EMPTY, lin) == GF_DUPE_EMPTY) break;
-  }
-  return false;
 }
 
 // The "unique" flags of a wavefront's sites (flag of site code lin: gdu[2 * (lin >> 4) + 1], bit 2 * (lin & 15)).
@@ -202,92 +110,9 @@ __device__ __forceinline__ void gf_bloom_insert(uint32_t* bloom, uint32_t nwords
   if ((__builtin_nontemporal_load(w) & b) != b) atomicOr(w, b);
 }
 
-// One block = one tile of GF_TILE_BASES window starts.  Phase 1 packs the tile's
-// ASCII bases (+ halo) into a 2-bit stream and an invalid-bit stream in LDS with
-// coalesced 16-byte loads; phase 2 cuts the windows out of LDS.
-// The FILL pass also sets the sites' "unique" flags and fills the presence filter (bloom != nullptr): every key's
-// first and last 14 bases in canonical form (gf_table.h) — a window enters its first 14 bases, and its last 14
-// only where window + 2, whose first 14 they are, has no key; both strands of a window share the canonical forms.
-template <int MODE>
-__global__ __launch_bounds__(GF_INDEX_THREADS) void gf_k_index_sites(GfGenes G, uint64_t* slots,
-                                                                     uint32_t nbuckets,
-                                                                     uint32_t* dupes, uint32_t* gdu,
-                                                                     uint32_t* bloom, uint32_t bloom_words) {
-  __shared__ uint32_t s_codes[GF_TILE_BASES / 16 + 2];
-  __shared__ uint32_t s_inv[GF_TILE_BASES / 32 + 2];
-  const uint32_t t0 = blockIdx.x * GF_TILE_BASES;
-  const int tid = threadIdx.x;
-
-  for (int ch = tid; ch < GF_TILE_BASES / 16 + 1; ch += GF_INDEX_THREADS) {
-    // cat is padded so that this 16-byte load stays inside the allocation
-    uint4 q = *(const uint4*)(G.cat + (size_t)t0 + 16u * ch);
-    uint32_t c0, c1, c2, c3, i0, i1, i2, i3;
-    gf_convert4(q.x, c0, i0);
-    gf_convert4(q.y, c1, i1);
-    gf_convert4(q.z, c2, i2);
-    gf_convert4(q.w, c3, i3);
-    s_codes[ch] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
-    ((uint16_t*)s_inv)[ch] = (uint16_t)(i0 | (i1 << 4) | (i2 << 8) | (i3 << 12));
-  }
-  if (tid == 0) {
-    s_codes[GF_TILE_BASES / 16 + 1] = 0;
-    ((uint16_t*)s_inv)[GF_TILE_BASES / 16 + 1] = 0xFFFF;
-    ((uint16_t*)s_inv)[GF_TILE_BASES / 16 + 2] = 0xFFFF;
-    ((uint16_t*)s_inv)[GF_TILE_BASES / 16 + 3] = 0xFFFF;
-  }
-  __syncthreads();
-
-  for (int l0 = 0; l0 < GF_TILE_BASES; l0 += GF_INDEX_THREADS) {  // (every lane of a wave stays in the loop)
-    const int l = l0 + tid;
-    const uint32_t g = t0 + (uint32_t)l;
-    bool fwd = false, rev = false, next_has = false;
-    uint32_t key = 0, lin_f = 0, lin_r = 0;
-    if (g < G.total) {
-      // the invalid-base flags of bases l .. l+31 (the halo chunk beyond the tile is flagged invalid from
-      // base TILE + 16 on, the one after it entirely)
-      const uint32_t sh = (uint32_t)l & 31u;
-      const uint32_t lo_w = s_inv[l >> 5], hi_w = s_inv[(l >> 5) + 1];
-      const uint32_t inv = sh ? ((lo_w >> sh) | (hi_w << (32u - sh))) : lo_w;
-      if ((inv & 0xFFFFu) == 0) {
-        // gene of g: last c with gene_off[c] <= g
-        int lo = 0, hi = G.n_genes;  // invariant gene_off[lo] <= g < gene_off[hi]
-        while (hi - lo > 1) {
-          int mid = (lo + hi) >> 1;
-          if (G.gene_off[mid] <= g) lo = mid; else hi = mid;
-        }
-        const uint32_t f = g - G.gene_off[lo];
-        const uint32_t len = G.gene_off[lo + 1] - G.gene_off[lo];
-        if (f + GF_KMER <= len) {  // the window lies inside the gene
-          key = gf_window(s_codes[l >> 4], s_codes[(l >> 4) + 1], (uint32_t)l);
-          fwd = f + GF_KMER < len;  // forward windows 0 .. len-17 (indexer.rs:188)
-          rev = f >= 1;             // reverse windows i = len-16-f in 0 .. len-17
-          lin_f = G.lin_base[lo] + f;
-          lin_r = G.lin_base[lo] - (f + 15u);
-          // window + 2 has a key of its own (it then enters the 14 bases the two share).  In the tile's last
-          // two windows the flags of its last bases are beyond the halo: "no" there costs one more look-up.
-          next_has = ((inv >> 2) & 0xFFFFu) == 0 && f + 2 + GF_KMER <= len && l + 2 + GF_KMER <= GF_TILE_BASES + 16;
-        }
-      }
-    }
-    if (MODE == GF_MODE_COUNT) {
-      if (fwd) gf_insert_count(slots, nbuckets, key);
-      if (rev) gf_insert_count(slots, nbuckets, gf_revcomp_key(key));
-    } else {
-      const bool uf = fwd && gf_fill_site(slots, nbuckets, dupes, key, lin_f);
-      const bool ur = rev && gf_fill_site(slots, nbuckets, dupes, gf_revcomp_key(key), lin_r);
-      gf_wave_set_unique(gdu, uf, lin_f);
-      gf_wave_set_unique(gdu, ur, lin_r);
-      if (bloom && (fwd || rev)) {
-        gf_bloom_insert(bloom, bloom_words, key & 0x0FFFFFFFu);
-        if (!next_has) gf_bloom_insert(bloom, bloom_words, key >> 4);
-      }
-    }
-  }
-}
-
 // ---- the one-pass build: claim and site in one touch of the bucket ----
-// 97 % of the keys of a gene set have one site.  The COUNT / FILL pair touches every site's bucket twice — both
-// random 64-byte lines far from every cache — to learn the count before a site may be written.  Here the thread
+// 97 % of the keys of a gene set have one site.  A count pass and a fill pass would touch every site's bucket twice —
+// both random 64-byte lines far from every cache — to learn the count before a site may be written.  Here the thread
 // that claims a slot writes its site with the claim (the final form of a key with one site); a thread that finds
 // its key already there turns the slot into a counter (the first site moves to a side list with the thread's
 // own) or bumps it and adds its site to the list.  A sweep then hands out the duplicate lists, and the side list
@@ -295,7 +120,11 @@ __global__ __launch_bounds__(GF_INDEX_THREADS) void gf_k_index_sites(GfGenes G, 
 struct GfSideEntry { uint32_t key, lin; };
 
 // true: the slot was claimed for (key, lin), which is so far the key's only site; false: the key was there, the
-// site (and, for the thread that found the key with one site, that site) went to e0 / e1, ne = how many
+// site (and, for the thread that found the key with one site, that site) went to e0 / e1, ne = how many.
+// A bucket's slots are claimed in order (a slot is taken only by a thread that saw every slot before it
+// occupied), so the occupied slots are a prefix.  The eight slots are read at once — one round trip to the
+// bucket's 64-byte line in place of one per occupied slot — and the slot-by-slot search starts at the first
+// slot that was still empty in that snapshot; keys never change or leave, so a key seen there is there.
 __device__ __forceinline__ bool gf_insert_site(uint64_t* slots, uint32_t nbuckets, uint32_t key, uint32_t lin,
                                                GfSideEntry& e0, GfSideEntry& e1, int& ne) {
   uint32_t b = gf_bucket_of(key, nbuckets);
@@ -303,7 +132,9 @@ __device__ __forceinline__ bool gf_insert_site(uint64_t* slots, uint32_t nbucket
   ne = 0;
   for (uint32_t guard = 0; guard <= nbuckets; ++guard) {
     uint64_t* bucket = slots + (size_t)b * GF_SLOTS_PER_BUCKET;
-    const uint4* q = (const uint4*)bucket;  // a snapshot (see gf_insert_count)
+    // (plain loads: a stale line shows an earlier state of the bucket — fewer slots taken, never a wrong key —
+    //  and the CAS below finds out what a slot holds by now)
+    const uint4* q = (const uint4*)bucket;
     const uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
     const uint32_t lo[8] = {q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, q3.x, q3.z};
     const uint32_t hi[8] = {q0.y, q0.w, q1.y, q1.w, q2.y, q2.w, q3.y, q3.w};
@@ -371,8 +202,14 @@ __device__ __forceinline__ unsigned int gf_ix_wave_append_lds(bool want, unsigne
   return base + (unsigned int)__popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull));
 }
 
-// the tile loop of gf_k_index_sites with gf_insert_site; side / side_n: the global list and its fill (entries
-// beyond side_cap are counted, not written: the host checks the count)
+// One block = one tile of GF_TILE_BASES window starts.  Phase 1 packs the tile's
+// ASCII bases (+ halo) into a 2-bit stream and an invalid-bit stream in LDS with
+// coalesced 16-byte loads; phase 2 cuts the windows out of LDS and inserts their sites (gf_insert_site).
+// It also sets the sites' "unique" flags and fills the presence filter (bloom != nullptr): every key's
+// first and last 14 bases in canonical form (gf_table.h) — a window enters its first 14 bases, and its last 14
+// only where window + 2, whose first 14 they are, has no key; both strands of a window share the canonical forms.
+// side / side_n: the global list and its fill (entries beyond side_cap are counted, not written: the host checks
+// the count)
 __global__ __launch_bounds__(GF_INDEX_THREADS) void gf_k_index_insert(GfGenes G, uint64_t* slots, uint32_t nbuckets,
                                                                       uint32_t* gdu, uint32_t* bloom,
                                                                       uint32_t bloom_words, GfSideEntry* side,
@@ -493,7 +330,7 @@ __global__ void gf_k_index_side(const GfSideEntry* __restrict__ side, unsigned l
       if (atomicCAS(dupes + start + k, GF_DUPE_EMPTY, e.lin) != GF_DUPE_EMPTY) continue;
       // A list fills from its front (a thread takes entry k only after it saw 0 .. k-1 taken), so whoever takes
       // the LAST entry knows the list complete and sorts it here, ascending (reproducible content) — the sweep
-      // over the whole table that did this (gf_k_sort_dupes) was 0.1 ms of a cancer-sized build.
+      // over the whole table that once did this was 0.1 ms of a cancer-sized build.
       if (k == cnt - 1 && cnt > 1) {
         uint32_t d[GF_DUP_THRESHOLD];
 #pragma unroll
@@ -725,7 +562,7 @@ __global__ __launch_bounds__(256) void gf_k_index_strands(GfGenes G, const uint3
 // stats[0]=n_sites [1]=n_keys [2]=n_unique [3]=n_dupe_keys [4]=n_high [5]=n_dupe_sites
 // [6]=dupes cursor (the extent of dupes[] handed out, granules' unused ends included)
 #define GF_DUPE_GRANULE 512ull
-// One sweep over the table after the COUNT pass: counts -> unique / dupes(start in dupes[]) / HIGH, and the
+// One sweep over the table after the insert pass: counts -> unique / dupes(start in dupes[]) / HIGH, and the
 // statistics on the way.  A thread takes one bucket (8 consecutive slots = one 64-byte line), a block 256
 // buckets per round: the room in dupes[] for the round's 2..5-fold keys is ONE atomic on the shared counter (a
 // block scan hands out the parts).  The first form took one per wavefront: a quarter of a million same-address
@@ -759,8 +596,8 @@ __global__ __launch_bounds__(256) void gf_k_classify_assign(uint64_t* slots, uin
     }
 #pragma unroll
     for (int k = 0; k < 2 * NP; ++k) {
-      // a slot holds a count (two-pass build, or a key the one-pass build found more than once), or — one-pass
-      // build — the site of a key claimed once: type UNIQUE already, count 1
+      // a slot holds a count (a key the insert pass found more than once), or the site of a key claimed once:
+      // type UNIQUE already, count 1
       const bool claimed = ((val[k] & GF_VAL_LOW) >> GF_TYPE_SHIFT) == GF_TYPE_UNIQUE;
       const uint32_t c = claimed ? 1u : (val[k] & GF_VAL_LOW);
       cnt_of[k] = c;
@@ -840,23 +677,6 @@ __global__ __launch_bounds__(256) void gf_k_classify_assign(uint64_t* slots, uin
     unsigned long long x = 0;
     for (int w = 0; w < 4; ++w) x += s_part[threadIdx.x][w];
     if (x) atomicAdd(stats + threadIdx.x, x);
-  }
-}
-
-// Sort every duplicate list ascending so its content is reproducible.
-__global__ void gf_k_sort_dupes(const uint64_t* slots, uint64_t nslots, uint32_t* dupes) {
-  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nslots;
-       s += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t val = (uint32_t)slots[s];
-    if (((val & GF_VAL_LOW) >> GF_TYPE_SHIFT) != GF_TYPE_DUPES) continue;
-    uint32_t cnt = (val >> GF_DUPE_COUNT_SHIFT) & 7u;
-    uint32_t* d = dupes + (val & GF_DUPE_START_MASK);
-    for (uint32_t a = 1; a < cnt; ++a) {
-      uint32_t x = d[a];
-      uint32_t b = a;
-      while (b > 0 && d[b - 1] > x) { d[b] = d[b - 1]; --b; }
-      d[b] = x;
-    }
   }
 }
 

@@ -61,24 +61,12 @@ __device__ __forceinline__ int gf_lanes_below(uint64_t m) {
 typedef uint32_t gf_u32x4 __attribute__((ext_vector_type(4)));
 
 // One probe: the 64-byte bucket of `key`.  Returns the slot's val with the
-// overflow bit cleared, 0 when the key is absent.  NT = load the bucket with the
-// non-temporal hint (a line that is used once should not push the L2-resident presence
-// filter out).
-template <bool NT = false>
+// overflow bit cleared, 0 when the key is absent.
 __device__ __forceinline__ uint32_t gf_lookup(const GfTable& T, uint32_t key) {
   uint32_t b = gf_bucket_of(key, T.nbuckets);
   for (uint32_t guard = 0; guard <= T.nbuckets; ++guard) {
     const uint4* p = (const uint4*)(T.slots + (size_t)b * GF_SLOTS_PER_BUCKET);
-    uint4 q0, q1, q2, q3;
-    if (NT) {
-      const gf_u32x4* pv = (const gf_u32x4*)p;
-      const gf_u32x4 a0 = __builtin_nontemporal_load(pv), a1 = __builtin_nontemporal_load(pv + 1),
-                     a2 = __builtin_nontemporal_load(pv + 2), a3 = __builtin_nontemporal_load(pv + 3);
-      q0 = make_uint4(a0.x, a0.y, a0.z, a0.w); q1 = make_uint4(a1.x, a1.y, a1.z, a1.w);
-      q2 = make_uint4(a2.x, a2.y, a2.z, a2.w); q3 = make_uint4(a3.x, a3.y, a3.z, a3.w);
-    } else {
-      q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3];
-    }
+    const uint4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
     uint32_t r = 0;
     // slot = (key << 32) | val, little endian: .x/.z = val, .y/.w = key
     r = (q0.y == key && (q0.x & GF_VAL_LOW)) ? q0.x : r;
@@ -301,18 +289,12 @@ __device__ __forceinline__ int gf_first_pass_seed_verify(const GfTable& T, GfMap
     val[h] = 0;
   }
 
-#if defined(GF_ABLATE) && GF_ABLATE <= 2
-  return ((key[0] ^ key[1] ^ st[0] ^ (st[1] << 3)) == 0x12345677u) ? 1000 : -1;  // timing-only build: stop after key extraction
-#endif
   // seeds: windows 0, 16, 32, 48 (all inside the first probing phase)
   const bool seed = (lane & 15) == 0 && st[0] == GF_ST_UNKNOWN;
   if (seed) {
     val[0] = gf_lookup(T, key[0]);
     st[0] = GF_ST_PROBED;
   }
-#if defined(GF_ABLATE) && GF_ABLATE <= 3
-  return ((key[0] ^ key[1] ^ st[0] ^ (st[1] << 3) ^ val[0]) == 0x12345677u) ? 1000 : -1;  // timing-only: stop after the seed probes
-#endif
   int v1 = 0, v2 = 0;  // best two candidate counts (upper bounds of their final counts minus U)
   {
     const bool uniq = seed && (val[0] >> GF_TYPE_SHIFT) == GF_TYPE_UNIQUE;
@@ -350,9 +332,6 @@ __device__ __forceinline__ int gf_first_pass_seed_verify(const GfTable& T, GfMap
   const bool can1 = st[1] == GF_ST_UNKNOWN;
   const int open_votes = __popcll(__ballot(can0)) + __popcll(__ballot(can1));
   if (v1 + open_votes < GF_MAJOR_KEYS / 2 || v2 + open_votes < GF_MINOR_KEYS / 2) return -1;
-#if defined(GF_ABLATE) && GF_ABLATE <= 4
-  return ((key[0] ^ key[1] ^ st[0] ^ (st[1] << 3) ^ val[0] ^ val[1] ^ (uint32_t)v1) == 0x12345677u) ? 1000 : -1;  // timing-only
-#endif
 
   // probe what is still unknown: everything but the last 19 windows first
   const int tail0 = nwin - (GF_MAJOR_KEYS / 2 - 1);
@@ -781,13 +760,8 @@ __global__ __launch_bounds__(WAVES * 64, 8) void gf_k_map_reads_short(GfTable T,
       gf_stage_regs<LCAP>(S, cur_x0, cur_x1, ndw, lane);
       gf_wave_lds_sync();
       int nvotes;
-#if defined(GF_ABLATE) && GF_ABLATE <= 1
-      nvotes = -1;  // timing-only build: stop after staging the read in LDS
-      if (S.codes[lane & 7] == 0x12345678u) nvotes = 1000;
-#else
       if constexpr (PRODUCER == 1) nvotes = gf_first_pass_seed_verify<LCAP>(T, S, L, sh, lane);
       else nvotes = gf_first_pass_probe_all<LCAP>(T, S, L, sh, lane);
-#endif
       gf_finish_read<LCAP>(T, S, L, sh, nvotes, lane, r, counts, matches);
     }
     cur_off = nxt_off; cur_end = nxt_end; cur_x0 = nxt_x0; cur_x1 = nxt_x1;

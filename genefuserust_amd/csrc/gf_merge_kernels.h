@@ -156,11 +156,8 @@ __device__ __forceinline__ void gf_stage_tile(const uint4* __restrict__ src, uin
   }
 }
 
-#ifndef GF_MF_WAVES_PER_SIMD
-#define GF_MF_WAVES_PER_SIMD 4
-#endif
 template <int PW>
-__global__ __launch_bounds__(256, PW <= 10 ? GF_MF_WAVES_PER_SIMD : 3) void gf_k_merge_find_stream(const uint8_t* __restrict__ l_bases,
+__global__ __launch_bounds__(256, PW <= 10 ? 4 : 3) void gf_k_merge_find_stream(const uint8_t* __restrict__ l_bases,
                                                               const uint8_t* __restrict__ l_quals,
                                                               const int64_t* __restrict__ l_off,
                                                               const uint8_t* __restrict__ r_bases,

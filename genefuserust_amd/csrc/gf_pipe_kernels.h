@@ -38,10 +38,6 @@
 #include "gf_map_kernels.h"
 #include "gf_table.h"
 
-#ifndef GF_PROBE_NT
-#define GF_PROBE_NT false
-#endif
-
 // 16 flag bits -> the same flags at the even bit positions of a word (2-bit layout)
 __device__ __forceinline__ uint32_t gf_spread16(uint32_t x) {
   x &= 0xFFFFu;
@@ -112,15 +108,11 @@ __device__ __forceinline__ void gf_entry_load(const GfPipeEntryW<PW>* e, uint32_
   uint32_t w[4 * EW];
   // (non-temporal loads / stores of the entries — they are written once and read once — were measured on
   // IDX-C, where the filter half in use shares the L2 with them: 1.61 against 1.57 ms for the two filter
-  // launches; GF_ENTRY_NT builds that form)
+  // launches)
   const gf_u32x4* src = (const gf_u32x4*)e;
 #pragma unroll
   for (int j = 0; j < EW; ++j) {
-#ifdef GF_ENTRY_NT
-    const gf_u32x4 q = __builtin_nontemporal_load(src + j);
-#else
     const gf_u32x4 q = src[j];
-#endif
     w[4 * j] = q.x; w[4 * j + 1] = q.y; w[4 * j + 2] = q.z; w[4 * j + 3] = q.w;
   }
   r = w[0];
@@ -150,11 +142,7 @@ __device__ __forceinline__ void gf_entry_store(GfPipeEntryW<PW>* e, uint32_t r, 
   for (int j = 0; j < EW; ++j) {
     gf_u32x4 q;
     q.x = w[4 * j]; q.y = w[4 * j + 1]; q.z = w[4 * j + 2]; q.w = w[4 * j + 3];
-#ifdef GF_ENTRY_NT
-    __builtin_nontemporal_store(q, dst + j);
-#else
     dst[j] = q;
-#endif
   }
 }
 
@@ -243,21 +231,13 @@ __device__ __forceinline__ uint32_t gf_window_mask(int nwin, int k) {
 // which forms of the filter the seeds ask before their bucket probe: 3 = the L2-resident one (2) and the one beyond the
 // L2 (1); 2 = only the former.  A look-up of a filter that does not live in the L2 is a miss like the bucket probe it
 // is meant to spare — and the probe names the diagonal (r03: IDX-C is bound by missed lines, §5).
-#ifndef GF_SEED_FILTER_MASK
-#define GF_SEED_FILTER_MASK 2u
-#endif
-#ifndef GF_MID_SEEDS
-#define GF_MID_SEEDS 2  // seeds probed by seed+verify when the filter is not L2-resident (4 = all, as before r03)
+constexpr uint32_t GF_SEED_FILTER_MASK = 2u;
+constexpr int GF_MID_SEEDS = 2;  // seeds probed by seed+verify when the filter is not L2-resident (4 = all, as before r03)
 // (r03, IDX-C, ms per 20 M reads: PANEL 3.78 with four seeds, 3.50 with two, 3.68 with one; all-background 6.18 / 5.54 /
 //  5.27 — a background read pays a missed line per seed, an on-target read whose seeds name nothing pays the filter
 //  sweeps and two or three probes in gf_k_probe_buckets)
-#endif
-#ifndef GF_FILTER_AUX
-#define GF_FILTER_AUX 0  // cache policy bits of the inline filter's buffer loads (experiments: 1 sc0, 2 nt, 16 sc1)
-#endif
-#ifndef GF_SVS_WAVES_PER_SIMD
-#define GF_SVS_WAVES_PER_SIMD 4  // (four blocks per CU run anyway, see launch_flat: the registers of six are not needed)
-#endif
+constexpr int GF_FILTER_AUX = 0;  // cache policy bits of the inline filter's buffer loads (1 sc0, 2 nt, 16 sc1)
+constexpr int GF_SVS_WAVES_PER_SIMD = 4;  // (four blocks per CU run anyway, see launch_flat: the registers of six are not needed)
 // ---- the background reads' filter rounds, by queue (r04) ----
 // r04 measured what binds seed+verify: nine more vector instructions per filter look-up (no memory access) cost 14 % of
 // its time — the kernel is bound by instruction issue, and two thirds of its instructions were the two filter rounds
@@ -267,9 +247,7 @@ __device__ __forceinline__ uint32_t gf_window_mask(int nwin, int k) {
 // (the layout of a list entry, 64 bytes), and whenever 64 records wait, the wave runs ONE round for 64 of them, every
 // lane busy, each on its own record's round.  A record that outlives round 0 goes back into the queue for round 1;
 // one that outlives round 1 goes to the list as before; the others are decided ([]).  Same decisions, read by read.
-#ifndef GF_FQ_CAP
-#define GF_FQ_CAP 96  // records per wave: a tile adds at most 64 to at most 63 waiting (more: passes run first)
-#endif
+constexpr int GF_FQ_CAP = 96;  // records per wave: a tile adds at most 64 to at most 63 waiting (more: passes run first)
 
 template <int PW>
 __device__ __forceinline__ int gf_filter_queue_pass(const GfTable& T, gf_u32x4* s_q, int q_len, int lane,
@@ -474,11 +452,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
   constexpr int NT = GfPipeEntryW<PW>::NT;          // words of one bit per stride-2 window
   __shared__ __attribute__((aligned(16))) uint32_t s_pk_all[4][PK_WORDS];
   __shared__ uint32_t s_iv_all[4][IV_WORDS];
-#ifndef GF_SV_INLINE_ROUNDS
   constexpr bool QUEUED = PW == 10;  // the filter rounds of reads without a candidate diagonal go by queue (above)
-#else
-  constexpr bool QUEUED = false;     // (A/B build: the rounds inline, as in r03)
-#endif
   __shared__ gf_u32x4 s_q_all[QUEUED ? 4 : 1][QUEUED ? GF_FQ_CAP * 4 : 1];
   __shared__ unsigned int s_cnt;
   if (threadIdx.x == 0) s_cnt = 0;
@@ -549,16 +523,9 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
 #pragma unroll
         for (int k = 0; k < NLOAD; ++k) {  // all of the tile's loads in flight together
           const uint32_t c = (uint32_t)lane + 64u * (uint32_t)k;
-#if defined(GF_STAGE_AUX)  // experiments: the staging loads as buffer loads with explicit cache-policy bits (1 sc0, 2 nt, 16 sc1)
-          const __amdgpu_buffer_rsrc_t stage_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)(chunks * 16u), 0x00020000);
-          const auto t = __builtin_amdgcn_raw_buffer_load_b128(stage_rsrc, 16u * (c < chunks ? c : chunks - 1), 0, GF_STAGE_AUX);
-          q[k] = make_uint4(t[0], t[1], t[2], t[3]);
-#elif !defined(GF_STAGE_TEMPORAL)  // streamed once: keep the bases out of the way of the table and the filter
+          // streamed once: keep the bases out of the way of the table and the filter
           const gf_u32x4 t = __builtin_nontemporal_load((const gf_u32x4*)(src + (c < chunks ? c : chunks - 1)));
           q[k] = make_uint4(t.x, t.y, t.z, t.w);
-#else
-          q[k] = src[c < chunks ? c : chunks - 1];
-#endif
         }
 #pragma unroll
         for (int k = 0; k < NLOAD; ++k) {
@@ -597,12 +564,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
         if constexpr (HOLD) return pk_held[j];
         else return gf_cut_pk(s_pk, w0, sh, j);
       };
-#if defined(GF_ABLATE_SV) && GF_ABLATE_SV == 6  // timing only: staging and conversion, one LDS word per read
-      if (in_range) counts[r] = s_pk[((uint32_t)(off0 - base_off) + mis) >> 4] == 0x1234567u ? 1 : 0;
-      if (false) {
-#else
       if (in_range) {
-#endif
         const int64_t len64 = off1 - off0;
         if (T.skip != nullptr && T.skip[r] > 0) {
           counts[r] = 0;  // not a candidate of this pass (gf_table.h: skip)
@@ -671,17 +633,6 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
               z_cur = z_next;
             }
           }
-#if defined(GF_ABLATE_SV) && GF_ABLATE_SV == 1
-          if ((nvalid ^ key[0] ^ key[1] ^ key[2] ^ key[3] ^ cwb[0] ^ cwb[1] ^ cwb[2] ^ cwb[NT - 1] ^ okm) == 0x1234567u) counts[r] = 1;
-          okm = 0;
-#endif
-#if defined(GF_ABLATE_SV) && GF_ABLATE_SV == 5  // timing only: staging, conversion, the windows and seeds of every read
-          if ((nvalid ^ key[0] ^ key[1] ^ key[2] ^ key[3] ^ cwb[0] ^ cwb[1] ^ cwb[2] ^ cwb[NT - 1] ^ okm) == 0x1234567u) counts[r] = 1;
-          okm = 0;
-          nvalid = 0;
-#pragma unroll
-          for (int k = 0; k < NT; ++k) cwb[k] = 0;
-#endif
           // The seeds go through the presence filter before their buckets (L2 hits).  The 14-mer
           // asked about (bases 32s+2 .. 32s+15) is the last 14 bases of window 16s and the first 14
           // of window 16s+1: a clear bit pair proves that neither can vote, which spares the filter
@@ -732,10 +683,6 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
                 kill[s >> 1] |= 3u << (16 * (s & 1));
               }
           }
-#if defined(GF_ABLATE_SV) && GF_ABLATE_SV == 3
-          if (okm == 0x1234567u) counts[r] = 1;
-          okm = 0;
-#endif
           // With a filter that lives beyond the L2 the seeds go to their buckets unasked, and then only GF_MID_SEEDS of
           // them (r03): a background read's four misses were a quarter of IDX-C's seed+verify; a read whose first
           // seeds name nothing gets its diagonal in gf_k_probe_buckets, if it outlives the filter sweeps.
@@ -761,10 +708,6 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
           nvalid -= __popc(cwb[0] & kill[0]) + __popc(cwb[1] & kill[1]);
           cwb[0] &= ~kill[0];
           cwb[1] &= ~kill[1];
-#if defined(GF_ABLATE_SV) && GF_ABLATE_SV == 4
-          if (K == 0x1234567u) counts[r] = 1;
-          K = GF_NONE_LIN;
-#endif
           // A read without a candidate diagonal (background, mostly) goes through the presence
           // filter right here: seed+verify is bound by L2-missing requests and leaves the L2's hit
           // bandwidth idle, which is exactly what the filter pass is short of.  Windows 8j .. 8j+7
@@ -772,17 +715,12 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
           // reach the gate.  Survivors carry the windows still standing and a flag that tells
           // gf_k_probe_filter to pass them on as they are.
           bool filt_done = false, filt_dead = false;
-#ifdef GF_ABLATE_EXTRA_VALU
-          uint32_t ablate_sink = 0;
-#endif
           const __amdgpu_buffer_rsrc_t filter_rsrc =
               __builtin_amdgcn_make_buffer_rsrc((void*)T.bloom, 0, (int)(T.bloom_words * 4u), 0x00020000);
           const uint32_t filter_bytes = T.bloom_words * 4u;
           uint32_t pp[NT];
 #pragma unroll
           for (int k = 0; k < NT; ++k) pp[k] = 0;
-#ifndef GF_SV_NO_INLINE_FILTER
-#ifndef GF_FILTER_ALLPAIRS
           // r03, reads of up to 160 bases: HALF the look-ups, and the bound of gf_table.h (gf_vote_bound_pairs)
           // in place of "fewer than 20 windows left".  Round 0 asks the even pairs of windows (0,1), (4,5),
           // (8,9) .. — the seeds' pairs, already answered, are among them — which leaves the odd pairs standing,
@@ -805,7 +743,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
               for (int k = 0; k < NT; ++k) pp_q[k] = cwb[k];
               K_q = Krep;
             } else if (khigh[0] | khigh[1]) {
-              // ... and no representative to go by (the two-pass build keeps none): the filter will call its every
+              // ... and no representative to go by (a slot whose representative field is all ones): the filter will call its every
               // window present — it skips the rounds and goes on as it is; the bucket pass strikes
               // its windows from one probe (gf_k_probe_buckets, r04).  Listing windows the filter was not asked about
               // as "filtered" is sound: the mark only says nobody need ask again.
@@ -820,63 +758,13 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
               pp_q[0] |= khigh[0];  // (in the table: they stand, as far as the bound's runs are concerned)
               pp_q[1] |= khigh[1];
             }
-          } else if (PW == 10 && K == GF_NONE_LIN && T.bloom_in_l2 == 2) {
-            filt_done = true;
-#pragma unroll
-            for (int k = 0; k < NT; ++k) pp[k] = cwb[k];
-            pp[0] |= khigh[0];  // (in the table: they stand, as far as the bound's runs are concerned)
-            pp[1] |= khigh[1];
-            bool alive = true;
-#pragma unroll 1
-            for (uint32_t rnd = 0; rnd < 2; ++rnd) {
-              if (alive) {
-                uint32_t wlo = pk_word(0);
-#pragma unroll
-                for (int j = 0; j < PW; ++j) {
-                  const uint32_t whi = j + 1 < PW ? pk_word(j + 1) : 0u;
-                  const uint32_t byte = (pp[j >> 2] >> (8 * (j & 3))) & 0xFFu;  // this word's 8 windows
-                  uint32_t word[2], bits[2];
-#pragma unroll
-                  for (int t = 0; t < 2; ++t) {
-                    // pair u = 2t + rnd of the word: windows 8j+2u, 8j+2u+1 share the 14-mer at bases 16j + 4u+2 ..
-                    const uint32_t s14 = __builtin_amdgcn_alignbit(whi, wlo, 16u * (uint32_t)t + 8u * rnd + 4u) & 0x0FFFFFFFu;
-                    const uint32_t h2 = GF_BLOOM_HASH((s14));
-#ifdef GF_ABLATE_EXTRA_VALU  // timing only: one more canonical form per look-up (8 vector instructions, no memory access)
-                    ablate_sink ^= gf_canon14(s14 ^ 0x05A5A5A5u);
-#endif
-                    bits[t] = GF_BLOOM_BITS(h2);
-                    const uint32_t nb = (byte & (3u << (4 * t + 2 * rnd))) ? filter_bytes : 0u;  // nobody to ask for: word 0
-                    word[t] = __builtin_amdgcn_raw_buffer_load_b32(filter_rsrc, __umulhi(h2, nb) & ~3u, 0, GF_FILTER_AUX);
-                  }
-                  uint32_t fail2 = 0;  // bit 2u: the filter rules out pair u's 14-mer
-#pragma unroll
-                  for (int t = 0; t < 2; ++t) {
-                    const uint32_t d = bits[t] & ~word[t];
-                    uint32_t f;
-                    asm("v_min_u32 %0, %1, 1" : "=v"(f) : "v"(d));
-                    fail2 |= f << (4 * t);
-                  }
-                  fail2 <<= 2 * rnd;
-                  pp[j >> 2] &= ~((fail2 | (fail2 << 1)) << (8 * (j & 3)));
-                  wlo = whi;
-                }
-                uint32_t x[NT];
-#pragma unroll
-                for (int k = 0; k < NT; ++k) x[k] = (pp[k] | (pp[k] >> 1)) & 0x55555555u;
-                alive = gf_vote_bound_pairs<4 * PW - 3>(x) >= GF_MAJOR_KEYS / 2;
-              }
-            }
-            filt_dead = !alive;
-          } else
-#endif
-          if (K == GF_NONE_LIN && T.bloom_in_l2 == 2) {
+          } else if (K == GF_NONE_LIN && T.bloom_in_l2 == 2) {
             filt_done = true;
             int npos = 0, rem = nvalid;
             uint32_t wlo = pk_word(0);
 #pragma unroll
             for (int j = 0; j < PW; ++j) {
               const uint32_t whi = j + 1 < PW ? pk_word(j + 1) : 0u;
-#ifndef GF_FILTER_OLD
               // (r02 e: the kernel's vector ALUs are busy 78 % of the time and this loop is half of their
               //  instructions.  The four answers of a word are gathered as fail bits on the even positions of one
               //  mask and applied to the word's window byte in one go — an and-not, a compare and a shift-or per
@@ -910,36 +798,9 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
                 rem -= __popc(byte);
                 filt_dead = npos + rem < GF_MAJOR_KEYS / 2;
               }
-#else
-              if (!filt_dead) {
-                const uint32_t byte = (cwb[j >> 2] >> (8 * (j & 3))) & 0xFFu;  // this word's 8 windows
-                uint32_t word[4], bits[4], both[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  both[u] = (byte >> (2 * u)) & 3u;
-                  // windows 8j+2u and 8j+2u+1 share the 14-mer at bases 16j + 4u+2 .. 16j + 4u+15
-                  const uint32_t s14 = __builtin_amdgcn_alignbit(whi, wlo, 8u * (uint32_t)u + 4u) & 0x0FFFFFFFu;
-                  const uint32_t h2 = GF_BLOOM_HASH((s14));
-                  bits[u] = GF_BLOOM_BITS(h2);
-                  word[u] = 0;
-                  if (both[u]) word[u] = T.bloom[GF_BLOOM_WORD(h2, T.bloom_words)];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                  const int cnt = (int)(both[u] & 1u) + (int)(both[u] >> 1);
-                  rem -= cnt;
-                  if (both[u] && (word[u] & bits[u]) == bits[u]) {
-                    pp[j >> 2] |= both[u] << (8 * (j & 3) + 2 * u);
-                    npos += cnt;
-                  }
-                }
-                filt_dead = npos + rem < GF_MAJOR_KEYS / 2;
-              }
-#endif
               wlo = whi;
             }
           }
-#endif
           // pass B: verify the candidate diagonal against the genes in site-code space, a
           // word of the read at a time: window w counts iff its 16 bases equal the bases of
           // site K + 2w and that site is the only site of its key
@@ -969,9 +830,6 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
             }
           }
           int v1 = 0;
-#ifdef GF_ABLATE_EXTRA_VALU
-          if (ablate_sink == 0x12345u) v1 = 1;
-#endif
 #pragma unroll
           for (int k = 0; k < NT; ++k) {
             vmb[k] &= cwb[k];  // windows that run past the end of the read compared garbage
@@ -1040,11 +898,7 @@ __global__ __launch_bounds__(256, PW <= 10 ? GF_SVS_WAVES_PER_SIMD : 4) void gf_
         }
       }
       const unsigned int slot_b = gf_wave_append_lds(undecided, &s_cnt);
-#ifdef GF_ENTRY_DIRECT_STORE
-      constexpr bool direct_store = true;
-#else
       constexpr bool direct_store = PW > 16;  // (the 20-word form has no registers to spare for the staging)
-#endif
       if constexpr (direct_store) {
         if (undecided) {
           uint32_t pkw[PW + 1];
@@ -1491,7 +1345,7 @@ __global__ __launch_bounds__(256) void gf_k_probe_buckets(GfTable T, const GfPip
         uint32_t val[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          if (act[u]) val[u] = gf_lookup<GF_PROBE_NT>(T, key[u]);
+          if (act[u]) val[u] = gf_lookup(T, key[u]);
         uint32_t K = GF_NONE_LIN;
         uint32_t Kh = GF_NONE_LIN;  // a copy of the repeat this read lies in: the diagonal of a HIGH key's representative site
 #pragma unroll

@@ -435,7 +435,7 @@ static FlatPlan flat_plan(int64_t n, int n_cus, int pw, bool long_reads) {
   FlatPlan p;
   // Up to 32 blocks per CU, but about 3 K reads a block at least and whole rounds of the four blocks a CU runs at a time:
   // 20 M reads in 6144 blocks were 1.4 % faster than in 8192 (the list kernels pay per block: 0.155 -> 0.133 ms),
-  // 200 M reads in 8192 blocks 0.4 % faster than in 6144 (r03 b; GF_NBLK_MULT sets blocks per CU outright: experiments)
+  // 200 M reads in 8192 blocks 0.4 % faster than in 6144 (r03 b; GF_NBLK_MULT sets blocks per CU outright: INTEGRATION.md)
   const int64_t round_blocks = (int64_t)n_cus * 4;
   int64_t nblk = std::min<int64_t>((int64_t)n_cus * 32, (n / 3072 + round_blocks / 2) / round_blocks * round_blocks);  // (the nearest whole round)
   nblk = std::max<int64_t>(nblk, round_blocks);
@@ -481,21 +481,13 @@ static int launch_flat(const gf_index* idx, const GfTable& T, hipStream_t st, co
   if (ev) GF_HIP(hipEventRecord(ev[0], st));
   // Four blocks per CU: r03 padded the PW = 10 kernel's LDS to get there (2.5 % faster than six); since r04 its queue
   // takes 24 KB itself — 40 KB per block, four per CU without padding (three cost 5.7 %, five or a smaller queue change
-  // nothing: the kernel is bound by instruction issue).  GF_SV_INLINE_ROUNDS builds, the r03 form, pad as before.
-#ifdef GF_SV_INLINE_ROUNDS
-  size_t pad_lds = PW == 10 ? 24000 : 0;
-#else
-  size_t pad_lds = 0;
-#endif
-  if (const char* e = getenv("GF_SV_PAD_LDS")) pad_lds = (size_t)atoi(e);  // experiments
-  hipLaunchKernelGGL((gf_k_seedverify_stream<PW, PACKED>), dim3(p.nblk), dim3(256), pad_lds, st, T, bases, src.pk, src.iv, offsets, n,
+  // nothing: the kernel is bound by instruction issue).
+  hipLaunchKernelGGL((gf_k_seedverify_stream<PW, PACKED>), dim3(p.nblk), dim3(256), 0, st, T, bases, src.pk, src.iv, offsets, n,
                      lmax, batch_max, counts, (GfPipeEntryW<PW>*)w.list_b, w.blk_cnt, p.per_block, w.list_long, w.ctr);
   if (ev) GF_HIP(hipEventRecord(ev[1], st));
   // a filter that does not fit an XCD's L2 (bloom_in_l2 == 1) is asked part by part, so that the part
-  // in use stays there (gf_k_probe_filter); GF_FILTER_PARTS sets the number of parts (experiments)
-  static const int parts_env = getenv("GF_FILTER_PARTS") ? atoi(getenv("GF_FILTER_PARTS")) : 0;
-  int nparts = T.bloom_in_l2 == 1 ? 2 : 1;
-  if (parts_env >= 1 && parts_env <= 8 && T.bloom_in_l2 == 1) nparts = parts_env;
+  // in use stays there (gf_k_probe_filter)
+  const int nparts = T.bloom_in_l2 == 1 ? 2 : 1;
   unsigned int *cnt_in = w.blk_cnt, *cnt_out = w.blk_cnt2;
   for (int ph = 0; ph < nparts; ++ph) {
     hipLaunchKernelGGL((gf_k_probe_filter<PW>), dim3(p.nblk), dim3(256), 0, st, T,
@@ -565,7 +557,6 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   };
   std::unique_ptr<gf_index> ix(new gf_index());
   ix->device = dev;
-  if (const char* e = getenv("GF_MAP_VARIANT")) ix->map_variant = atoi(e) >= 0 && atoi(e) <= 2 ? atoi(e) : 0;  // experiments
   {
     static std::atomic<int> cus_of[64];  // (hipGetDeviceProperties is 0.1 ms a call: once per device and process)
     int cus = dev < 64 ? cus_of[dev].load() : 0;
@@ -604,8 +595,7 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   ix->gene_len_h.assign(glen.begin(), glen.begin() + n_genes);
 
   // 8 slots per bucket, about 4 keys per bucket on average
-  uint64_t sites_per_bucket = 4;
-  if (const char* e = getenv("GF_SITES_PER_BUCKET")) sites_per_bucket = (uint64_t)std::max(1, std::min(7, atoi(e)));  // experiments
+  const uint64_t sites_per_bucket = 4;
   uint64_t nb64 = std::max<uint64_t>(16, (site_bound + sites_per_bucket - 1) / sites_per_bucket);
   if (nb64 > 0x7FFFFFFFull) return fail(GF_ERR_CAPACITY, "table too large");
   const uint32_t nbuckets = (uint32_t)nb64;
@@ -702,18 +692,13 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
     }
   }
   mark("gather threads started");
-  static const bool pull = getenv("GF_BUILD_DMA") == nullptr;  // (GF_BUILD_DMA=1: copies by the DMA engine + gf_k_upper_inplace, as before)
   for (int k = 0; k < nch; ++k) {
     if (!pooled) gather(k);
     else while (!chunk_done[(size_t)k].load(std::memory_order_acquire)) std::this_thread::yield();
     const uint64_t b0 = (uint64_t)k * CH, b1 = std::min<uint64_t>(b0 + CH, cat_bytes);  // (both multiples of 16)
-    if (pull) {
-      hipLaunchKernelGGL(gf_k_upper_copy, dim3((unsigned)(((b1 - b0) / 16 + 255) / 256)), dim3(256), 0, 0,
-                         (const uint8_t*)stage + b0, d_cat.p + b0, (unsigned long long)((b1 - b0) / 16));
-      GF_HIP(hipGetLastError());
-    } else {
-      GF_HIP(hipMemcpyAsync(d_cat.p + b0, stage + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, 0));
-    }
+    hipLaunchKernelGGL(gf_k_upper_copy, dim3((unsigned)(((b1 - b0) / 16 + 255) / 256)), dim3(256), 0, 0,
+                       (const uint8_t*)stage + b0, d_cat.p + b0, (unsigned long long)((b1 - b0) / 16));
+    GF_HIP(hipGetLastError());
   }
   mark("last chunk queued");
   uint32_t* meta = (uint32_t*)(stage + ((cat_bytes + 63) & ~(size_t)63));
@@ -728,11 +713,6 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   GF_HIP(hipMemcpyAsync(ix->d_lin_base, m_lb, lin_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, 0));
   GF_HIP(hipMemcpyAsync(ix->d_lin_hi, m_lh, lin_hi.size() * sizeof(uint32_t), hipMemcpyHostToDevice, 0));
   GF_HIP(hipMemcpyAsync(ix->d_gene_len, m_gl, glen.size() * sizeof(uint32_t), hipMemcpyHostToDevice, 0));
-  if (!pull) {
-    hipLaunchKernelGGL(gf_k_upper_inplace, dim3((unsigned)std::min<size_t>((cat_bytes / 16 + 255) / 256, 4096)), dim3(256), 0, 0,
-                       d_cat.p, (unsigned long long)(cat_bytes / 16));
-    GF_HIP(hipGetLastError());
-  }
 
   lap("alloc, memset, copies in");
   GfGenes G;
@@ -748,9 +728,8 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   hipLaunchKernelGGL(gf_k_index_strands, dim3((unsigned)((gd_words + 255) / 256)), dim3(256), 0, 0, G,
                      (const uint32_t*)ix->d_lin_hi, ix->d_gdu, (uint32_t)gd_words);
   GF_HIP(hipGetLastError());
-  // One pass (default): a site is written with the claim of its key's slot; the sites of keys found again go
-  // through a side list (gf_index_kernels.h).  GF_BUILD_TWO_PASS=1: the COUNT / FILL pair (experiments).
-  static const bool two_pass = getenv("GF_BUILD_TWO_PASS") != nullptr;
+  // One pass: a site is written with the claim of its key's slot; the sites of keys found again go
+  // through a side list (gf_index_kernels.h).
   uint32_t bloom_words = 0, bloom_in_l2 = 0;
   // presence filter over canonical 14-mers, filled with the sites.  Indexes up to ~14 M keys: <= GF_BLOOM_KIB
   // (default 3 MiB) so that it lives in every XCD's L2, and seed+verify runs the filter pass for reads
@@ -758,22 +737,21 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   // GF_BLOOM_MID_KIB (default 8 MiB) — no longer L2-resident, but still mostly L2 hits: used for
   // the seeds and by the filter kernel, which asks it half by half so that the half in use does
   // stay in the L2 (IDX-C, 29 M keys: 5.0 G reads/s; 4.65 in one pass).  Larger indexes: about
-  // GF_BLOOM_BIG_BPK (default 4) bits per key, resident in the Infinity Cache and used by the
+  // 4 bits per key, resident in the Infinity Cache and used by the
   // filter kernel only — a lookup is then an L2-missing request like a bucket probe, but one
   // lookup answers for two windows and a negative answer spares both bucket probes.
-  // (`keys`: the number of keys where it is known before the filter is filled — the two-pass build — and the
-  // number of sites, 3 % more on these gene sets, where it is not.)
+  // (`keys`: the number of sites, 3 % more than the keys on these gene sets — the keys are not counted before the
+  // filter is filled.)
   auto make_filter = [&](uint64_t keys) -> int {
-    size_t kib = 3072, mid_kib = 8192, big_bpk = 4;
+    size_t kib = 3072, mid_kib = 8192;
+    const size_t big_bpk = 4;
     if (const char* e = getenv("GF_BLOOM_KIB")) kib = (size_t)atol(e);
     if (const char* e = getenv("GF_BLOOM_MID_KIB")) mid_kib = (size_t)atol(e);
-    if (const char* e = getenv("GF_BLOOM_BIG_BPK")) big_bpk = (size_t)atol(e);
     const uint64_t cap_words = (uint64_t)kib * 1024 / 4, mid_words = (uint64_t)mid_kib * 1024 / 4;
     const uint64_t want_words = keys * 7 / 128;  // 1.75 bits per key: what the L2-resident form needs at least
     // beyond that: 2.2 bits per key — at 1.75 half of the background reads outlive the filter and
     // go on to the buckets (IDX-C: buckets 0.64 -> 0.37 ms, filter 1.48 -> 1.58 ms per 20 M reads)
-    uint64_t mid_bpk100 = 220;
-    if (const char* e = getenv("GF_BLOOM_BPK100")) mid_bpk100 = (uint64_t)atol(e);  // experiments
+    const uint64_t mid_bpk100 = 220;
     const uint64_t want_mid = keys * mid_bpk100 / 3200;
     uint64_t words = std::min(std::max<uint64_t>(1024, keys / 2), cap_words);  // up to 16 bits per key
     if (kib > 0 && want_words <= cap_words) {
@@ -781,11 +759,10 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
     } else if (kib > 0 && want_mid <= mid_words) {
       words = want_mid;
       // (r03, measured on IDX-C with the vote bound's half look-ups: asking this filter from seed+verify itself,
-      //  GF_BLOOM_INLINE_MID=1, 3.87 ms per 20 M reads at 1.5 bits per key, 4.13 at 2.2; the sweeps over the list
+      //  3.87 ms per 20 M reads at 1.5 bits per key, 4.13 at 2.2; the sweeps over the list
       //  3.93 at 2.2 — no winner: about half of an 8 MiB filter's look-ups miss a 4 MiB L2 either way)
-      static const bool inline_mid = getenv("GF_BLOOM_INLINE_MID") && atoi(getenv("GF_BLOOM_INLINE_MID")) == 1;
-      bloom_in_l2 = inline_mid ? 2 : 1;
-    } else if (kib > 0 && big_bpk > 0) {
+      bloom_in_l2 = 1;
+    } else if (kib > 0) {
       words = std::min<uint64_t>(keys * big_bpk / 32 + 1024, (64ull << 20) / 4);
     } else {
       words = 0;
@@ -807,39 +784,32 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   struct SideBlock { int dev; GfSideEntry* p = nullptr; ~SideBlock() { if (p) { (void)hipDeviceSynchronize(); block_free(dev, p); } } } d_side{dev};
   const uint64_t side_cap = std::max<uint64_t>(site_bound, 1);
   uint64_t n_side = 0;
-  if (!two_pass) {
-    if (int rc = make_filter(site_bound)) return rc;
-    GF_HIP(block_alloc(dev, (void**)&d_side.p, side_cap * sizeof(GfSideEntry)));
-    // The filter first, by partitions and without global atomics (gf_index_kernels.h), in the side list's block,
-    // which the insert pass only then starts to fill.  (Filters beyond 8 MiB — whole-genome-sized indexes — and
-    // GF_FILTER_ATOMIC=1 keep the fill inside the insert pass.)
-    static const bool filter_atomic = getenv("GF_FILTER_ATOMIC") != nullptr;
-    bool filter_parted = false;
-    unsigned int* d_part_fill = (unsigned int*)(d_stats.p + 8);  // (cleared with the statistics)
-    if (ix->d_bloom && ntiles > 0 && !filter_atomic && bloom_words <= GF_FPARTS_MAX * GF_FSLICE_WORDS) {
-      const uint32_t nparts = (bloom_words + GF_FSLICE_WORDS - 1) / GF_FSLICE_WORDS;
-      const uint64_t room = side_cap * (sizeof(GfSideEntry) / sizeof(uint32_t)) / nparts;  // hashes per partition the block holds
-      const uint64_t want = 2 * ((total + total / 8) / nparts) + 1024;  // twice an even share of (a little over) one hash per base
-      const uint32_t part_cap = (uint32_t)std::min<uint64_t>(std::min(room, want), 0x7FFFFFFFull);
-      if (part_cap > 0) {
-        hipLaunchKernelGGL(gf_k_filter_scatter, dim3(ntiles), dim3(GF_INDEX_THREADS), 0, 0, G, ix->d_bloom, bloom_words, nparts,
-                           (uint32_t*)d_side.p, part_cap, d_part_fill);
-        GF_HIP(hipGetLastError());
-        hipLaunchKernelGGL(gf_k_filter_build, dim3(nparts), dim3(1024), 0, 0, ix->d_bloom, bloom_words,
-                           (const uint32_t*)d_side.p, part_cap, (const unsigned int*)d_part_fill);
-        GF_HIP(hipGetLastError());
-        filter_parted = true;
-      }
-    }
-    if (ntiles > 0) {
-      hipLaunchKernelGGL(gf_k_index_insert, dim3(ntiles), dim3(GF_INDEX_THREADS), 0, 0, G, ix->d_slots, nbuckets, ix->d_gdu,
-                         filter_parted ? (uint32_t*)nullptr : ix->d_bloom, bloom_words, d_side.p, d_stats.p + 7,
-                         (unsigned long long)side_cap);
+  if (int rc = make_filter(site_bound)) return rc;
+  GF_HIP(block_alloc(dev, (void**)&d_side.p, side_cap * sizeof(GfSideEntry)));
+  // The filter first, by partitions and without global atomics (gf_index_kernels.h), in the side list's block,
+  // which the insert pass only then starts to fill.  (Filters beyond 8 MiB — whole-genome-sized indexes —
+  // keep the fill inside the insert pass.)
+  bool filter_parted = false;
+  unsigned int* d_part_fill = (unsigned int*)(d_stats.p + 8);  // (cleared with the statistics)
+  if (ix->d_bloom && ntiles > 0 && bloom_words <= GF_FPARTS_MAX * GF_FSLICE_WORDS) {
+    const uint32_t nparts = (bloom_words + GF_FSLICE_WORDS - 1) / GF_FSLICE_WORDS;
+    const uint64_t room = side_cap * (sizeof(GfSideEntry) / sizeof(uint32_t)) / nparts;  // hashes per partition the block holds
+    const uint64_t want = 2 * ((total + total / 8) / nparts) + 1024;  // twice an even share of (a little over) one hash per base
+    const uint32_t part_cap = (uint32_t)std::min<uint64_t>(std::min(room, want), 0x7FFFFFFFull);
+    if (part_cap > 0) {
+      hipLaunchKernelGGL(gf_k_filter_scatter, dim3(ntiles), dim3(GF_INDEX_THREADS), 0, 0, G, ix->d_bloom, bloom_words, nparts,
+                         (uint32_t*)d_side.p, part_cap, d_part_fill);
       GF_HIP(hipGetLastError());
+      hipLaunchKernelGGL(gf_k_filter_build, dim3(nparts), dim3(1024), 0, 0, ix->d_bloom, bloom_words,
+                         (const uint32_t*)d_side.p, part_cap, (const unsigned int*)d_part_fill);
+      GF_HIP(hipGetLastError());
+      filter_parted = true;
     }
-  } else if (ntiles > 0) {
-    hipLaunchKernelGGL(gf_k_index_sites<GF_MODE_COUNT>, dim3(ntiles), dim3(GF_INDEX_THREADS), 0, 0, G,
-                       ix->d_slots, nbuckets, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
+  }
+  if (ntiles > 0) {
+    hipLaunchKernelGGL(gf_k_index_insert, dim3(ntiles), dim3(GF_INDEX_THREADS), 0, 0, G, ix->d_slots, nbuckets, ix->d_gdu,
+                       filter_parted ? (uint32_t*)nullptr : ix->d_bloom, bloom_words, d_side.p, d_stats.p + 7,
+                       (unsigned long long)side_cap);
     GF_HIP(hipGetLastError());
   }
   // (few blocks: each ends with seven atomics on the same seven addresses, 14 ns apiece and one after the other —
@@ -855,37 +825,22 @@ int gf_index_build(const char* const* gene_seqs, const int64_t* gene_lens, int32
   }
   stage_drain.armed = false;
   stage_lock.unlock();
-  lap(two_pass ? "strands, count pass, list assignment + statistics" : "strands, insert pass (sites, flags, filter), list assignment + statistics");
+  lap("strands, insert pass (sites, flags, filter), list assignment + statistics");
   const uint64_t dupes_extent = stats[6];  // (>= stats[5], the sites in the lists: granules end unused)
   if (dupes_extent > dupes_cap)
     return fail(GF_ERR_CAPACITY, "too many duplicated sites for the 26-bit duplicate index");
   GF_HIP(hipMemsetAsync(ix->d_dupes, 0xFF, std::max<uint64_t>(dupes_extent, 1) * sizeof(uint32_t), 0));
-  if (!two_pass) {
-    n_side = stats[7];
-    if (n_side > side_cap) return fail(GF_ERR_CAPACITY, "side list of the index build overflowed");
-    if (n_side > 0) {
-      const int grid = (int)std::min<uint64_t>((n_side + 255) / 256, (uint64_t)ix->n_cus * 16);
-      hipLaunchKernelGGL(gf_k_index_side, dim3(grid), dim3(256), 0, 0, (const GfSideEntry*)d_side.p, (unsigned long long)n_side,
-                         ix->d_slots, nbuckets, ix->d_dupes, ix->d_gdu);
-      GF_HIP(hipGetLastError());
-    }
-    lap("side list (duplicate lists, flags)");
-  } else {
-    if (int rc = make_filter(stats[1])) return rc;
-    if (ntiles > 0) {
-      hipLaunchKernelGGL(gf_k_index_sites<GF_MODE_FILL>, dim3(ntiles), dim3(GF_INDEX_THREADS), 0, 0, G,
-                         ix->d_slots, nbuckets, ix->d_dupes, ix->d_gdu, ix->d_bloom, bloom_words);
-      GF_HIP(hipGetLastError());
-    }
-    lap("fill pass (sites, unique flags, filter)");
-  }
-  if (two_pass) {  // (the one-pass build sorts a list as its last site arrives: gf_k_index_side)
-    hipLaunchKernelGGL(gf_k_sort_dupes, dim3(sweep_grid), dim3(256), 0, 0, ix->d_slots, nslots, ix->d_dupes);
+  n_side = stats[7];
+  if (n_side > side_cap) return fail(GF_ERR_CAPACITY, "side list of the index build overflowed");
+  if (n_side > 0) {  // (a duplicate list is sorted as its last site arrives)
+    const int grid = (int)std::min<uint64_t>((n_side + 255) / 256, (uint64_t)ix->n_cus * 16);
+    hipLaunchKernelGGL(gf_k_index_side, dim3(grid), dim3(256), 0, 0, (const GfSideEntry*)d_side.p, (unsigned long long)n_side,
+                       ix->d_slots, nbuckets, ix->d_dupes, ix->d_gdu);
     GF_HIP(hipGetLastError());
   }
+  lap("side list (duplicate lists, flags)");
   // the strands + flags once more in overlapping tiles, now that the flags are final (gf_table.h: gdt)
-  static const bool gdu_tiles = !(getenv("GF_GDU_TILES") && atoi(getenv("GF_GDU_TILES")) == 0);  // (0: experiments)
-  if (gdu_tiles) {
+  {
     const uint32_t n_tiles = (uint32_t)((gd_words + GF_GDT_STRIDE - 1) / GF_GDT_STRIDE) + 1;
     GF_HIP(block_alloc(dev, (void**)&ix->d_gdt, (size_t)n_tiles * 128));
     hipLaunchKernelGGL(gf_k_gdu_tiles, dim3((n_tiles * 16u + 255u) / 256u), dim3(256), 0, 0, (const uint2*)ix->d_gdu,
@@ -1314,7 +1269,6 @@ struct ZeroCopy {
   // the call in flight (zc_submit .. zc_wait)
   const uint8_t* h_counts = nullptr;
   const gf_seqmatch* h_matches = nullptr;
-  bool flag_wait = false;
   void release() {
     if (pinned) (void)hipHostFree(pinned);
     if (d_done_ctr) (void)hipFree(d_done_ctr);
@@ -1494,18 +1448,15 @@ static int stage_and_map(gf_index* mix, HostLane& L, const char* bases, const in
 static int64_t small_call_reads() {
   static const int64_t v = [] {
     int64_t d = 64;
-    if (const char* e = getenv("GF_SMALL_CALL_READS")) d = std::max<int64_t>(0, atoll(e));  // experiments
+    if (const char* e = getenv("GF_SMALL_CALL_READS")) d = std::max<int64_t>(0, atoll(e));
     return d;
   }();
   return v;
 }
 #define GF_SMALL_CALL_READS small_call_reads()
-#ifndef GF_PACK_CALL_READS_DEFAULT
-#define GF_PACK_CALL_READS_DEFAULT 8192  // (reads: packs of up to 4096 pairs; the crossover is measured by tools/bench_pack_sweep.py)
-#endif
 static int64_t pack_call_reads() {
   static const int64_t v = [] {
-    int64_t d = GF_PACK_CALL_READS_DEFAULT;
+    int64_t d = 8192;  // (reads: packs of up to 4096 pairs; the crossover is measured by tools/bench_pack_sweep.py)
     if (const char* e = getenv("GF_PACK_CALL_READS")) d = std::max<int64_t>(0, atoll(e));  // 0 = the batch route for every call beyond the small ones
     return d;
   }();
@@ -1542,14 +1493,10 @@ static int zc_submit(gf_index* mix, ZeroCopy& Z, hipStream_t st, const char* bas
   memset(h_cnt, 0, (size_t)n);  // (the kernels write the counts of the reads with segments only: GfTable::done_flag)
   uint8_t* d = Z.d_pinned;
   GfTable T = mix->table;
-  static const bool flag_wait = !(getenv("GF_PACK_WAIT") && !strcmp(getenv("GF_PACK_WAIT"), "sync"));  // experiments
-  Z.flag_wait = flag_wait;
   Z.seq += 1;
-  if (flag_wait) {
-    T.done_ctr = Z.d_done_ctr;
-    T.done_flag = (unsigned int*)d;
-    T.done_seq = Z.seq;
-  }
+  T.done_ctr = Z.d_done_ctr;
+  T.done_flag = (unsigned int*)d;
+  T.done_seq = Z.seq;
   const uint8_t* d_b = d_src ? d_src : (const uint8_t*)(d + (h_b - Z.pinned));
   const int64_t* d_off = (const int64_t*)(d + sz_flag);
   uint8_t* d_cnt = d + (h_cnt - Z.pinned);
@@ -1578,22 +1525,20 @@ static int zc_submit(gf_index* mix, ZeroCopy& Z, hipStream_t st, const char* bas
 static int zc_wait(ZeroCopy& Z, hipStream_t st) {
   bool done = false;
   const uint32_t* h_flag = (const uint32_t*)Z.pinned;
-  if (Z.flag_wait) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint64_t spin = 1;; ++spin) {
-      if (__atomic_load_n(h_flag, __ATOMIC_ACQUIRE) == Z.seq) { done = true; break; }
-      __builtin_ia32_pause();
-      // a kernel that takes longer than a pack's few tens of microseconds (the device is busy with somebody's batch):
-      // the core goes to whoever else wants it between looks
-      if (spin > 4096) std::this_thread::yield();
-      if ((spin & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-    }
-    if (done && ++Z.unsynced >= 64) done = false;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint64_t spin = 1;; ++spin) {
+    if (__atomic_load_n(h_flag, __ATOMIC_ACQUIRE) == Z.seq) { done = true; break; }
+    __builtin_ia32_pause();
+    // a kernel that takes longer than a pack's few tens of microseconds (the device is busy with somebody's batch):
+    // the core goes to whoever else wants it between looks
+    if (spin > 4096) std::this_thread::yield();
+    if ((spin & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
   }
+  if (done && ++Z.unsynced >= 64) done = false;
   if (!done) {
     GF_HIP(hipStreamSynchronize(st));
     Z.unsynced = 0;
-    if (Z.flag_wait && __atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != Z.seq)
+    if (__atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != Z.seq)
       return fail(GF_ERR_HIP, "a zero-copy call's kernel ended without reporting completion");
   }
   return GF_OK;
@@ -2357,13 +2302,9 @@ static int scan_pairs_impl(const gf_index* idx, const void* d_l_bases, const voi
   GF_HIP(hipGetLastError());
   // The retries — a few per ten thousand pairs, every one a read that does map — go straight to the exact
   // wave-per-read kernel, as many as there are (the count is on the device).  Through the flat pipeline like the other
-  // passes (GF_RETRY_FLAT=1) they cost 0.41 ms per 10 M pairs: launches over retry_cap mostly empty slots, and a
+  // passes they cost 0.41 ms per 10 M pairs: launches over retry_cap mostly empty slots, and a
   // bucket kernel whose every lane walks a junction read's thirty windows one probe after the other.
-  static const bool retry_flat = getenv("GF_RETRY_FLAT") != nullptr;
-  if (retry_flat) {
-    rc = map_reads_device_impl(idx, rb, r_off, retry_cap, (int32_t)std::max<int64_t>(merged_max, 1), cR, mR, stream, nullptr);
-    if (rc != GF_OK) return rc;
-  } else {
+  {
     GfTable T = idx->table;
     T.skip = nullptr;
     T.fixed_len = 0;

@@ -58,7 +58,7 @@ def main():
         elif name.startswith("gf_k_merge_find"):
             cur = {"stage": "scan_pairs_device", "k": []}
             stages.append(cur)
-        elif name.startswith(("gf_k_index_", "gf_k_classify", "gf_k_sort_dupes", "gf_k_filter_", "gf_k_upper_", "gf_k_pair_hits_finish")):
+        elif name.startswith(("gf_k_index_", "gf_k_classify", "gf_k_filter_", "gf_k_upper_", "gf_k_pair_hits_finish")):
             cur = None   # (the index build; the device tail, which bench_pairs.py times as a stage of its own)
         if cur is not None:
             cur["k"].append(i)
