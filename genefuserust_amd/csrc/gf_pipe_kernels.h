@@ -1309,7 +1309,14 @@ __global__ __launch_bounds__(256) void gf_k_probe_buckets(GfTable T, const GfPip
 #pragma unroll
       for (int k = 0; k < NT; ++k) { p0[k] = p[k]; voted[k] = 0; }
       bool dead = (v1 + left < GF_MAJOR_KEYS / 2) || (v2 + left < GF_MINOR_KEYS / 2);
-      while (!dead && left > 0) {
+      // A read that has its diagonal cannot lose votes: h never falls and a HIGH strike only lowers `left`, so once
+      // v1 + h and v2 + h meet both gates no probe can make it die — it goes to the exact kernel at once instead of
+      // being probed to its last window (a junction read, a read over a duplicated stretch: up to 17 dependent round
+      // trips that its whole wave waited for).  Not while the diagonal is still wanted: finding K takes nh out of h.
+      auto cannot_die = [&]() {
+        return !want_k && v1 + h >= GF_MAJOR_KEYS / 2 && v2 + h >= GF_MINOR_KEYS / 2;
+      };
+      while (!dead && left > 0 && !cannot_die()) {
         // the read dies only after at least `need` more probes miss: issue that many (up to
         // 4) bucket probes together instead of one round trip each
         const int needA = v1 + h + left - (GF_MAJOR_KEYS / 2 - 1);

@@ -4,6 +4,7 @@
 # 1) rocprofv3 --kernel-trace --stats of the default bench command
 # 2) separate --pmc passes for HBM traffic (FETCH_SIZE / WRITE_SIZE cannot share a pass)
 # Summaries land in gpurun_out/prof_<tag>/ ; copy what is to be judged into profiles/.
+# Every profiler run has a time limit of its own (STEP_LIMIT seconds, default 600), and a failed one ends the script.
 set -o pipefail
 TAG=${1:-r01}
 REPO=$(pwd)
@@ -24,7 +25,7 @@ json.dump({"kernel_src_sha": bench.kernel_source_sha(), "lib_sha": bench.library
           open(sys.argv[1] + "/build_stamp.json", "w"))
 PY
 echo "== kernel trace ==" 
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH > $OUT/trace_bench.log 2>&1 || { echo trace failed; tail -20 $OUT/trace_bench.log; exit 1; }
+timeout -k 10 ${STEP_LIMIT:-600} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH > $OUT/trace_bench.log 2>&1 || { echo trace failed; tail -20 $OUT/trace_bench.log; exit 1; }
 # (r03: TCC_BUBBLE = the 128-byte read requests FETCH_SIZE's gfx950 formula relies on; the _DRAM_32B counter
 #  tallies a 64-byte request as 2 and a 128-byte one as 4, i.e. bytes / 32 whatever the request size)
 SETS=("FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum"
@@ -39,7 +40,7 @@ fi
 for pmc in "${SETS[@]}"; do
   name=$(echo $pmc | tr ' ' '_' | cut -c1-40)
   echo "== pmc $pmc =="
-  rocprofv3 --pmc $pmc --output-format csv -d $OUT/pmc_$name -o pmc -- $BENCH > $OUT/pmc_${name}.log 2>&1 || { echo "pmc $pmc failed"; tail -5 $OUT/pmc_${name}.log; }
+  timeout -k 10 ${STEP_LIMIT:-600} rocprofv3 --pmc $pmc --output-format csv -d $OUT/pmc_$name -o pmc -- $BENCH > $OUT/pmc_${name}.log 2>&1 || { echo "pmc $pmc failed"; tail -5 $OUT/pmc_${name}.log; exit 1; }
 done
 cd $REPO
 python3 tools/summarize_profile.py $OUT > $OUT/summary.txt 2>&1
