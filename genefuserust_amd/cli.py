@@ -4,7 +4,8 @@ The options of the reference (src/argparse.rs) keep their letters and defaults â
 ``--help`` only â€” and the flow is that of src/genefuse.rs: the input files are checked, the command line is printed,
 the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired or single-end), the HTML report and
 the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
-out: the device, the streamed routes, where ``.gz`` files are inflated and where the report tail runs.
+out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, and the
+whole-genome alignable filter.
 """
 from __future__ import annotations
 
@@ -56,6 +57,9 @@ def parser() -> argparse.ArgumentParser:
     own.add_argument("--remove-alignables", action="store_true", help="apply the reference's last filter (paired-end, "
                      "one CSV, whole reference).  Off by default: the reference's Matcher, as it is, removes nothing on "
                      "a genome and panics on small references")
+    own.add_argument("--alignable-filter", choices=("genome",), default=None, help="genome: drop the matches whose read "
+                     "lies end to end somewhere in the reference, tested on the device (one CSV, whole reference).  "
+                     "Off by default")
     return p
 
 
@@ -89,10 +93,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
+            if args.alignable_filter is not None:
+                raise ValueError("alignable_filter: only the scans of one CSV have this filter")
             out = scan_multi_csv_report(args.ref, args.fusion, args.read1, args.read2, **common)   # (streams its files)
         else:
             out = scan_report(args.ref, args.fusion, args.read1, args.read2, route=args.route,
-                              remove_alignables=args.remove_alignables, **common)
+                              remove_alignables=args.remove_alignables, **common,
+                              **({"alignable_filter": args.alignable_filter} if args.alignable_filter else {}))
     except (ValueError, FileNotFoundError) as e:
         print("ERROR: %s" % e, file=sys.stderr)
         return 1

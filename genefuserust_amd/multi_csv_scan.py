@@ -323,7 +323,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: str = "", device: int = -1,
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
                 chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
-                originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False):
+                originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False, *,
+                alignable_filter: str = None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -335,8 +336,13 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     ``originals``: the matches carry their FASTQ records, in every mode (``scan.scan_pair_end_files``).  ``html_file``:
     ``report_html`` goes there, before the JSON, as ``json_file`` does.  ``route``: the single-end scanner's
     (``scan.scan_single_end_files``).  ``remove_alignables``: the paired-end scanner's (``scan.scan_pair_end_files``);
-    ``ValueError`` in the other modes, which do not have it."""
+    ``ValueError`` in the other modes, which do not have it.  ``alignable_filter``: None or "genome", the whole-genome
+    alignable filter on the device of the single-CSV scanners (``scan.scan_pair_end_files``); ``ValueError`` for a list
+    of CSVs."""
     from . import scan
+    from .alignable import need_filter
+    if need_filter(alignable_filter, remove_alignables) and _rust_stem_ext(fusion_file)[2] != "csv":
+        raise ValueError("alignable_filter: only the scans of one CSV have this filter")
     if remove_alignables and not (_rust_stem_ext(fusion_file)[2] == "csv" and read2_file):
         raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
     if _rust_stem_ext(fusion_file)[2] == "csv":
@@ -344,11 +350,13 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
             results, counters = scan.scan_pair_end_report(ref_file, fusion_file, read1_file, read2_file, device, settings,
                                                           chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
                                                           inflate=inflate, tail=tail, originals=originals,
-                                                          remove_alignables=remove_alignables)
+                                                          remove_alignables=remove_alignables,
+                                                          alignable_filter=alignable_filter)
         else:
             results, counters = scan.scan_single_end_report(ref_file, fusion_file, read1_file, device, settings, route,
                                                             chunk_bytes=chunk_bytes, ref_chunk_bytes=ref_chunk_bytes,
-                                                            inflate=inflate, tail=tail, originals=originals)
+                                                            inflate=inflate, tail=tail, originals=originals,
+                                                            alignable_filter=alignable_filter)
         if html_file:
             write_report(html_file, report_html(results, command, version, time, settings))
         if json_file:

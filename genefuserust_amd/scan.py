@@ -112,17 +112,24 @@ def route_counters(count_key: str, n: int, n_found: int, tot: dict = None, chunk
 
 
 def finish_matches(found: List[ReadMatch], mapper, deletion_threshold: int, remove_alignables: bool, before: dict,
-                   after: dict, tail: str = "host") -> Tuple[List[ReadMatch], dict]:
+                   after: dict, tail: str = "host", *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
     """The tail of every route: the filters, (matches kept in ``sort_matches`` order, counters).  ``tail``: "host", a
     library call per match and per comparison; "device", the reasons of all matches in one call on the index's device
-    and the order through ``numpy.lexsort`` (report_tail.py) — the same matches and counters."""
-    from . import report_tail
+    and the order through ``numpy.lexsort`` (report_tail.py) — the same matches and counters.  ``alignable_filter``:
+    None, or "genome": the reads of the matches that the other filters keep are tested against the whole reference in
+    one call on the index's device (alignable.py), the alignable ones dropped and counted as ``genome_alignables``
+    behind the filter counts; ``ValueError`` for anything else, and together with ``remove_alignables``."""
+    from . import alignable, report_tail
+    genome = alignable.need_filter(alignable_filter, remove_alignables)
     if report_tail.need_tail(tail):
         kept, removed = report_tail.filter_matches_device(found, deletion_threshold, mapper.m_indexer.info()["device"])
     else:
         kept, removed = mapper.filter_matches(found, deletion_threshold)
     if remove_alignables:  # (the reference always does: a whole-genome scan that removes nothing)
         kept, removed["alignables"] = mapper.remove_alignables(kept)
+    if genome:
+        kept, removed["genome_alignables"] = alignable.remove_genome_alignables(
+            kept, mapper.m_indexer.get_ref(), mapper.m_indexer.info()["device"])
     sort = report_tail.order_matches if tail == "device" else mapper.sort_matches
     return sort(kept), {**before, **removed, **after}
 
@@ -219,11 +226,22 @@ def _route_inflate(inflate, chunk_bytes, ref_chunk_bytes):
     return (inflate if chunk_bytes is not None else "host"), (inflate if ref_chunk_bytes is not None else "host")
 
 
+def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) -> None:
+    """``ValueError`` for an ``alignable_filter`` that ``finish_matches`` refuses, and for the genome filter with a
+    streamed reference: before any file is opened."""
+    from .alignable import need_filter
+    if need_filter(alignable_filter, remove_alignables) and ref_chunk_bytes is not None:
+        raise ValueError("alignable_filter=%r needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
+                         "reference" % (alignable_filter,))
+
+
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
-                      chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False):
+                      chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
+                      alignable_filter=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
     from .report_tail import need_tail
     need_tail(tail)
+    _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
                          "reference")
@@ -240,7 +258,7 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
             produced = pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
                 ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
-                                        tail=tail)
+                                        tail=tail, alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
 
 
@@ -248,7 +266,7 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         deletion_threshold: int = 50, remove_alignables: bool = False,
                         chunk_bytes: int = None, ref_chunk_bytes: int = None,
                         inflate: str = "host", tail: str = "host",
-                        originals: bool = False) -> Tuple[List[ReadMatch], dict]:
+                        originals: bool = False, *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -276,34 +294,44 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     ``originals``: every match also carries ``m_original_reads``, the FASTQ records of both mates of its pair as
     (name, sequence, strand, quality) — what the HTML report shows under a supporting read.  The whole-file route cuts
     them from the host text; the streamed route gathers them on the device behind each chunk's scan
-    (``hit_names.hit_records_device``).  The same on every route; without it nothing more is queued or allocated."""
+    (``hit_names.hit_records_device``).  The same on every route; without it nothing more is queued or allocated.
+
+    ``alignable_filter``: None (the default), or "genome": a last filter that works, on the device (alignable.py) — a
+    match whose read lies end to end somewhere in the reference (either strand, fewer than 10 bases outside exact
+    16-base windows, no indels) is dropped and counted as ``genome_alignables``.  It needs whole contigs: ``ValueError``
+    with ``ref_chunk_bytes``, with ``remove_alignables`` (the reference's own filter as it is), and for any other
+    value."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
-                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals)[:2]
+                             remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
+                             alignable_filter)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                          settings: Settings = None, chunk_bytes: int = None, ref_chunk_bytes: int = None,
                          inflate: str = "host", tail: str = "host", originals: bool = False,
-                         remove_alignables: bool = False) -> Tuple[List[FusionResult], dict]:
+                         remove_alignables: bool = False, *,
+                         alignable_filter: str = None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
     the reference's stdout block, JSON file and HTML file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``,
     ``originals`` (what ``report_html`` shows under the supporting reads), ``remove_alignables`` (the reference's last
-    filter as it is): see ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all
+    filter as it is), ``alignable_filter`` (a last filter that works): see ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all
     groups in one host call, the refined breaks of all matches in one ``gf_rp_adjust_device`` call (report_tail.py);
     the same results, counters and report bytes."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
                                              settings.deletion_threshold, remove_alignables, chunk_bytes,
-                                             ref_chunk_bytes, inflate, tail, originals), settings, tail, device)
+                                             ref_chunk_bytes, inflate, tail, originals, alignable_filter),
+                          settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                        ref_chunk_bytes=None, inflate="host", tail="host", originals=False):
+                        ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     from .report_tail import need_tail
     need_tail(tail)
+    _need_whole_contigs(alignable_filter, False, ref_chunk_bytes)
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
     if chunk_bytes is not None and route != "device":
@@ -317,7 +345,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
             produced = single_end_found(ix, mapper, *FastqReader(read1_file).read_all_device(ix), originals)
         else:
             produced = _single_end_host_found(mapper, *FastqReader(read1_file).read_all_device(ix), originals)
-        kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail)
+        kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail,
+                                        alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
 
 
@@ -325,7 +354,7 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           deletion_threshold: int = 50, route: str = "device",
                           chunk_bytes: int = None, ref_chunk_bytes: int = None,
                           inflate: str = "host", tail: str = "host",
-                          originals: bool = False) -> Tuple[List[ReadMatch], dict]:
+                          originals: bool = False, *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -339,19 +368,21 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     ``chunks``.  ``ref_chunk_bytes`` (either route): the reference FASTA in chunks, see ``scan_pair_end_files``.
     ``inflate``: where the streamed ``.gz`` files are inflated, see ``scan_pair_end_files``.  ``tail``: where the
     filters and the sort run, see ``scan_pair_end_files``.  ``originals``: every match carries its read's FASTQ
-    record in ``m_original_reads``, on every route; see ``scan_pair_end_files``."""
+    record in ``m_original_reads``, on every route; see ``scan_pair_end_files``.  ``alignable_filter``: None or
+    "genome", the whole-genome alignable filter on the device; see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                               ref_chunk_bytes, inflate, tail, originals)[:2]
+                               ref_chunk_bytes, inflate, tail, originals, alignable_filter)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                            settings: Settings = None, route: str = "device", chunk_bytes: int = None,
                            ref_chunk_bytes: int = None, inflate: str = "host",
-                           tail: str = "host", originals: bool = False) -> Tuple[List[FusionResult], dict]:
+                           tail: str = "host", originals: bool = False, *,
+                           alignable_filter: str = None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``, ``originals``: see ``scan_single_end_files``; ``tail``: see
+    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``: see ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
-                                               route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals),
-                          settings, tail, device)
+                                               route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
+                                               alignable_filter), settings, tail, device)
