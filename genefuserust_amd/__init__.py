@@ -15,5 +15,6 @@ from .matcher import Matcher, MatcherPanic, remove_alignables  # noqa: F401
 from .fastq import FastqBatch, FastqReader, FastqReaderPair, fastq_cut_device, record_lines  # noqa: F401
 from .multi_csv_scan import (PreparedPairs, prepare_pairs_device, read_csv_list, report_names,  # noqa: F401
                              scan_multi_csv_report, scan_prepared_pairs_device, scan_report)
+from .read_filter import ReadFilter, filter_reads_device  # noqa: F401
 
 __version__ = "0.1.0"

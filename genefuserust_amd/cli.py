@@ -4,8 +4,8 @@ The options of the reference (src/argparse.rs) keep their letters and defaults â
 ``--help`` only â€” and the flow is that of src/genefuse.rs: the input files are checked, the command line is printed,
 the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired or single-end), the HTML report and
 the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
-out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, and the
-whole-genome alignable filter.
+out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, the
+whole-genome alignable filter, and the quality filter of the reads ahead of the scan.
 """
 from __future__ import annotations
 
@@ -60,7 +60,35 @@ def parser() -> argparse.ArgumentParser:
     own.add_argument("--alignable-filter", choices=("genome",), default=None, help="genome: drop the matches whose read "
                      "lies end to end somewhere in the reference, tested on the device (one CSV, whole reference).  "
                      "Off by default")
+    rf = p.add_argument_group("the read filter (off by default; any of its options switches it on)")
+    rf.add_argument("--read-filter", action="store_true", help="filter and trim the reads on the device ahead of the "
+                    "scan, with the defaults below: poly-G and low-quality tails are cut off, pairs with a mate that "
+                    "is too short, holds too many N or too many low bases are not scanned")
+    rf.add_argument("--qualified-phred", type=int, default=None, help="a base below this phred is a low base, default 15")
+    rf.add_argument("--unqualified-percent", type=int, default=None, help="the share of low bases a read may have, "
+                    "default 40")
+    rf.add_argument("--n-base-limit", type=int, default=None, help="the most N bases a read may have, default 5")
+    rf.add_argument("--length-required", type=int, default=None, help="the shortest read kept, default 15")
+    rf.add_argument("--cut-tail-window", type=int, default=None, help="cut a read behind its last window of this many "
+                    "bases that reaches --cut-tail-mean; 1 to 64, default 0: off")
+    rf.add_argument("--cut-tail-mean", type=int, default=None, help="the mean phred a tail window must reach, default 20")
+    rf.add_argument("--poly-g-min", type=int, default=None, help="cut off a poly-G tail of at least this many bases, "
+                    "default 10; 0: off")
     return p
+
+
+READ_FILTER_OPTIONS = ("qualified_phred", "unqualified_percent", "n_base_limit", "length_required", "cut_tail_window",
+                       "cut_tail_mean", "poly_g_min")
+
+
+def _read_filter(args):
+    """The ``ReadFilter`` the options ask for, None when none of them is given; ``ValueError`` for a value out of
+    range."""
+    given = {k: getattr(args, k) for k in READ_FILTER_OPTIONS if getattr(args, k) is not None}
+    if not (args.read_filter or given):
+        return None
+    from .read_filter import ReadFilter
+    return ReadFilter(**given)
 
 
 def _missing(args) -> Optional[str]:
@@ -90,6 +118,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                   version=__version__, time=now, chunk_bytes=args.chunk_bytes, ref_chunk_bytes=args.ref_chunk_bytes,
                   inflate=args.inflate, tail=args.tail, originals=bool(args.html))
     try:
+        read_filter = _read_filter(args)
+        if read_filter is not None:   # (off: the calls of today)
+            common["read_filter"] = read_filter
         if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")

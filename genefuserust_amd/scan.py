@@ -111,6 +111,22 @@ def route_counters(count_key: str, n: int, n_found: int, tot: dict = None, chunk
     return before, after
 
 
+def filtered_reads(ix: Indexer, read_filter, *batches):
+    """The ``FastqBatch``es (a file's records, or a pair's) through the read filter on the index's device
+    (read_filter.py): (the batches it leaves, ``counted(produced)``).  ``counted`` adds the filter's seven totals to
+    the end of a producer's counters in front of the filter counts.  ``read_filter`` None: the batches as they are,
+    nothing queued, and ``counted`` changes nothing."""
+    if read_filter is None:
+        return batches, lambda produced: produced
+    from .read_filter import filter_reads_device, totals_counters
+    *kept, totals = filter_reads_device(ix, read_filter, *batches)
+
+    def counted(produced):
+        found, before, after = produced
+        return found, {**before, **totals_counters(totals.cpu().tolist())}, after
+    return tuple(kept), counted
+
+
 def finish_matches(found: List[ReadMatch], mapper, deletion_threshold: int, remove_alignables: bool, before: dict,
                    after: dict, tail: str = "host", *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
     """The tail of every route: the filters, (matches kept in ``sort_matches`` order, counters).  ``tail``: "host", a
@@ -196,26 +212,36 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
 
 
 def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
-                   originals: bool = False) -> Tuple[List[ReadMatch], dict, dict]:
+                   originals: bool = False, *, read_filter=None) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
     order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
-    ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``)."""
+    ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``).
+    ``read_filter``: a ``ReadFilter``, every chunk's records go through the read filter ahead of the scan
+    (``scan_stream._scan_chunk``) and its totals, summed over the chunks, end the counters in front of the filter
+    counts."""
+    from .read_filter import COUNTER_KEYS
     from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
     count_key = "pairs" if len(files) == 2 else "reads"
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
     found: List[ReadMatch] = []
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
+    if read_filter is not None:
+        sums.update(dict.fromkeys(COUNTER_KEYS, 0))
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        # (originals=False is not passed on: the stream is then called as it always was)
+        # (originals=False and read_filter=None are not passed on: the stream is then called as it always was)
         for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
-                                                     **({"originals": True} if originals else {})):
+                                                     **({"originals": True} if originals else {}),
+                                                     **({"read_filter": read_filter} if read_filter is not None else {})):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
             chunks += 1
-    return (found, *route_counters(count_key, sums[count_key], len(found), sums, chunks))
+    before, after = route_counters(count_key, sums[count_key], len(found), sums, chunks)
+    if read_filter is not None:
+        before.update({k: sums[k] for k in COUNTER_KEYS})
+    return found, before, after
 
 
 def _route_inflate(inflate, chunk_bytes, ref_chunk_bytes):
@@ -237,10 +263,12 @@ def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) ->
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
                       chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
-                      alignable_filter=None):
+                      alignable_filter=None, read_filter=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
+    from .read_filter import need_read_filter
     from .report_tail import need_tail
     need_tail(tail)
+    need_read_filter(read_filter)
     _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
@@ -249,14 +277,16 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
     with open_index(ref_file, fusion_csv, device, ref_chunk_bytes, ref_inflate) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
-            produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate, originals)
+            produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate, originals,
+                                      **({"read_filter": read_filter} if read_filter is not None else {}))
         else:
-            reads = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
-            (l, _), (r, _) = reads
+            (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
+            (l, r), counted = filtered_reads(ix, read_filter, l, r)
+            reads = (l, ltext), (r, rtext)
             max_len = max(l.max_read_len(), r.max_read_len(), 1)
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
-            produced = pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
-                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)
+            produced = counted(pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
+                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
                                         tail=tail, alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -266,7 +296,8 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         deletion_threshold: int = 50, remove_alignables: bool = False,
                         chunk_bytes: int = None, ref_chunk_bytes: int = None,
                         inflate: str = "host", tail: str = "host",
-                        originals: bool = False, *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
+                        originals: bool = False, *, alignable_filter: str = None,
+                        read_filter=None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -300,37 +331,50 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     match whose read lies end to end somewhere in the reference (either strand, fewer than 10 bases outside exact
     16-base windows, no indels) is dropped and counted as ``genome_alignables``.  It needs whole contigs: ``ValueError``
     with ``ref_chunk_bytes``, with ``remove_alignables`` (the reference's own filter as it is), and for any other
-    value."""
+    value.
+
+    ``read_filter``: None (the default), or a ``read_filter.ReadFilter``: the records go through a quality filter on
+    the device between the FASTQ cut and the scan (read_filter.py) — poly-G and low-quality tails are cut off, and a
+    pair with a mate that is then too short, holds too many N or too many low bases is scanned as two empty reads.
+    The record indices stay, so names and ``m_original_reads`` are those of the records as the sequencer wrote them.
+    The counters gain ``reads_passed``, ``reads_trimmed``, ``bases_trimmed``, ``reads_too_short``,
+    ``reads_too_many_n``, ``reads_low_quality`` and ``reads_mate_failed`` in front of the filter counts, the same on
+    every route; ``pairs`` keeps counting every record.  ``ValueError`` for anything else.  Without it nothing more is
+    queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
                              remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
-                             alignable_filter)[:2]
+                             alignable_filter, read_filter)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                          settings: Settings = None, chunk_bytes: int = None, ref_chunk_bytes: int = None,
                          inflate: str = "host", tail: str = "host", originals: bool = False,
                          remove_alignables: bool = False, *,
-                         alignable_filter: str = None) -> Tuple[List[FusionResult], dict]:
+                         alignable_filter: str = None, read_filter=None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
     the reference's stdout block, JSON file and HTML file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``,
     ``originals`` (what ``report_html`` shows under the supporting reads), ``remove_alignables`` (the reference's last
-    filter as it is), ``alignable_filter`` (a last filter that works): see ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all
+    filter as it is), ``alignable_filter`` (a last filter that works), ``read_filter`` (a quality filter ahead of the
+    scan): see ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all
     groups in one host call, the refined breaks of all matches in one ``gf_rp_adjust_device`` call (report_tail.py);
     the same results, counters and report bytes."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
                                              settings.deletion_threshold, remove_alignables, chunk_bytes,
-                                             ref_chunk_bytes, inflate, tail, originals, alignable_filter),
-                          settings, tail, device)
+                                             ref_chunk_bytes, inflate, tail, originals, alignable_filter,
+                                             read_filter), settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                        ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None):
+                        ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None,
+                        read_filter=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
+    from .read_filter import need_read_filter
     from .report_tail import need_tail
     need_tail(tail)
+    need_read_filter(read_filter)
     _need_whole_contigs(alignable_filter, False, ref_chunk_bytes)
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
@@ -340,11 +384,15 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
     with open_index(ref_file, fusion_csv, device, ref_chunk_bytes, ref_inflate) as (ix, fusions):
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
-            produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate, originals)
-        elif route == "device":
-            produced = single_end_found(ix, mapper, *FastqReader(read1_file).read_all_device(ix), originals)
-        else:
-            produced = _single_end_host_found(mapper, *FastqReader(read1_file).read_all_device(ix), originals)
+            produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate, originals,
+                                      **({"read_filter": read_filter} if read_filter is not None else {}))
+        else:   # (both routes start from the records in HBM, where the read filter runs)
+            b, text = FastqReader(read1_file).read_all_device(ix)
+            (b,), counted = filtered_reads(ix, read_filter, b)
+            if route == "device":
+                produced = counted(single_end_found(ix, mapper, b, text, originals))
+            else:
+                produced = counted(_single_end_host_found(mapper, b, text, originals))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail,
                                         alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -354,7 +402,8 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           deletion_threshold: int = 50, route: str = "device",
                           chunk_bytes: int = None, ref_chunk_bytes: int = None,
                           inflate: str = "host", tail: str = "host",
-                          originals: bool = False, *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
+                          originals: bool = False, *, alignable_filter: str = None,
+                          read_filter=None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -369,20 +418,22 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     ``inflate``: where the streamed ``.gz`` files are inflated, see ``scan_pair_end_files``.  ``tail``: where the
     filters and the sort run, see ``scan_pair_end_files``.  ``originals``: every match carries its read's FASTQ
     record in ``m_original_reads``, on every route; see ``scan_pair_end_files``.  ``alignable_filter``: None or
-    "genome", the whole-genome alignable filter on the device; see ``scan_pair_end_files``."""
+    "genome", the whole-genome alignable filter on the device; see ``scan_pair_end_files``.  ``read_filter``: None or a
+    ``ReadFilter``, the quality filter ahead of the scan, on either route; see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                               ref_chunk_bytes, inflate, tail, originals, alignable_filter)[:2]
+                               ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                            settings: Settings = None, route: str = "device", chunk_bytes: int = None,
                            ref_chunk_bytes: int = None, inflate: str = "host",
                            tail: str = "host", originals: bool = False, *,
-                           alignable_filter: str = None) -> Tuple[List[FusionResult], dict]:
+                           alignable_filter: str = None, read_filter=None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``: see ``scan_single_end_files``; ``tail``: see
+    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``: see
+    ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
                                                route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
-                                               alignable_filter), settings, tail, device)
+                                               alignable_filter, read_filter), settings, tail, device)
