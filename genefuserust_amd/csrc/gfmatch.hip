@@ -30,6 +30,7 @@
 #include "gf_map_kernels.h"
 #include "gf_merge_kernels.h"
 #include "gf_fastq_kernels.h"
+#include "gf_host_batch.h"
 #include "gf_host_pack.h"
 #include "gf_pipe_kernels.h"
 #include "gf_pair_kernels.h"
@@ -1255,6 +1256,36 @@ static const uint8_t* pinned_device_address(const char* p, size_t len) {
   return nullptr;
 }
 
+void* gf_host_alloc(int64_t bytes) {
+  if (bytes <= 0) return nullptr;
+  void* p = nullptr;
+  if (hipHostMalloc(&p, (size_t)bytes, hipHostMallocDefault) != hipSuccess) {
+    g_err = "hipHostMalloc failed";
+    return nullptr;
+  }
+  void* d = nullptr;
+  if (hipHostGetDevicePointer(&d, p, 0) == hipSuccess && d) {  // known to the zero-copy calls: they read it in place
+    std::unique_lock<std::shared_mutex> lk(g_pinned_mu);
+    g_pinned.push_back({(const char*)p, (size_t)bytes, (const uint8_t*)d});
+  } else {
+    (void)hipGetLastError();
+  }
+  return p;
+}
+
+void gf_host_free(void* p) {
+  if (!p) return;
+  {
+    std::unique_lock<std::shared_mutex> lk(g_pinned_mu);
+    for (size_t i = 0; i < g_pinned.size(); ++i)
+      if (g_pinned[i].host == (const char*)p) {
+        g_pinned.erase(g_pinned.begin() + (long)i);
+        break;
+      }
+  }
+  (void)hipHostFree(p);
+}
+
 // A zero-copy call: reads staged in (or read straight from) pinned host memory, ONE launch of the exact
 // wave-per-read kernels that fetches them over the link and writes counts and matches back into the same pinned
 // block, completion reported by a word the kernel's last block stores (GfTable::done_*) — no copy commands, no
@@ -1347,32 +1378,57 @@ LaneLease::~LaneLease() {
   ix->lane_cv.notify_one();
 }
 
+// the regions of a staged batch (gf_host_batch.h: gf_staged_layout) in a lane's or a stream slot's device arena
 struct HostStage {
-  uint8_t* bases = nullptr;     // device pointer such that bases + offsets[r] is read r (host offsets kept as they are)
-  int64_t* offsets = nullptr;
-  uint8_t* counts = nullptr;
-  gf_seqmatch* matches = nullptr;
-  gf_hit* hits = nullptr;
-  int64_t* total = nullptr;
-  uint8_t* compact_ws = nullptr;
+  uint8_t *bases, *counts, *compact_ws;
+  int64_t *offsets, *total;
+  gf_seqmatch* matches;
+  gf_hit* hits;
+};
+static HostStage stage_at(void* arena, const gf_staged_layout& a) {
+  uint8_t* p = (uint8_t*)arena;
+  return {p + a.bases, p + a.counts, p + a.compact_ws, (int64_t*)(p + a.offsets), (int64_t*)(p + a.total),
+          (gf_seqmatch*)(p + a.matches), (gf_hit*)(p + a.hits)};
+}
+
+// However a call ends in an error, nothing of it is in flight on its stream when it returns: a lane call's copies land
+// in local pageable buffers and the lane goes back to the pool; a stream submit's copies read the caller's
+// pinned pk / iv / offsets, which the caller may reuse at once; a zero-copy call's kernels read the caller's
+// gf_host_alloc block and write the lane's or slot's pinned block.  `zc`: a zero-copy call that failed
+// between its launches may leave d_done_ctr standing, and the next one could never report: it is zeroed on the drained
+// stream.  Z.seq stays advanced; the completion word holds that number or an earlier one, never the next call's.
+struct Drain {
+  hipStream_t st;
+  ZeroCopy* zc = nullptr;
+  bool armed = true;
+  ~Drain() {
+    if (!armed) return;
+    (void)hipStreamSynchronize(st);
+    if (zc && zc->d_done_ctr && hipMemsetAsync(zc->d_done_ctr, 0, 256, st) == hipSuccess) (void)hipStreamSynchronize(st);
+    if (zc) zc->unsynced = 0;
+  }
 };
 
-static int lane_reserve(HostLane& L, size_t need) {
-  if (L.arena_bytes >= need) return GF_OK;
-  if (L.arena) {
-    GF_HIP(hipStreamSynchronize(L.st));
-    GF_HIP(hipFree(L.arena));
-    L.arena = nullptr;
-    L.arena_bytes = 0;
+// sizes the lane's grow-only arena for the pack and carves it
+static int lane_stage(HostLane& L, const gf_pack_span& P, int64_t hits_cap, HostStage& S) {
+  const gf_staged_layout a = gf_staged_layout_for(P.n, P.b1 - P.b0, hits_cap, gf_compact_workspace_bytes(P.n));
+  if (L.arena_bytes < a.bytes) {
+    if (L.arena) {
+      GF_HIP(hipStreamSynchronize(L.st));
+      GF_HIP(hipFree(L.arena));
+      L.arena = nullptr;
+      L.arena_bytes = 0;
+    }
+    const size_t want = a.bytes + a.bytes / 4;  // (slack: see acquire_workspace)
+    if (hipMalloc(&L.arena, want) == hipSuccess) {
+      L.arena_bytes = want;
+    } else {
+      (void)hipGetLastError();
+      GF_HIP(hipMalloc(&L.arena, a.bytes));
+      L.arena_bytes = a.bytes;
+    }
   }
-  const size_t want = need + need / 4;  // (slack: see acquire_workspace)
-  if (hipMalloc(&L.arena, want) == hipSuccess) {
-    L.arena_bytes = want;
-  } else {
-    (void)hipGetLastError();
-    GF_HIP(hipMalloc(&L.arena, need));
-    L.arena_bytes = need;
-  }
+  S = stage_at(L.arena, a);
   return GF_OK;
 }
 
@@ -1398,43 +1454,39 @@ static int zc_reserve(ZeroCopy& Z, hipStream_t st, size_t need) {
   return GF_OK;
 }
 
-// validates the batch, sizes the lane's arena, queues the copies in and the mapping on the lane's stream
-static int stage_and_map(gf_index* mix, HostLane& L, const char* bases, const int64_t* offsets, int64_t n,
-                         int64_t hits_cap, HostStage& S) {
-  if (n < 0) return fail(GF_ERR_ARG, "negative n");
-  if (n > 0 && (!offsets)) return fail(GF_ERR_ARG, "offsets is null");
-  int64_t maxlen = 0;
-  for (int64_t r = 0; r < n; ++r) {
-    int64_t l = offsets[r + 1] - offsets[r];
-    if (l < 0) return fail(GF_ERR_ARG, "offsets must be non-decreasing");
-    maxlen = std::max(maxlen, l);
+// the answer of either half of the one check of a pack (gf_host_batch.h), a refusal's message kept for gf_last_error
+static int pack_fail(int rc) {
+  return rc == GF_OK ? rc : fail(rc, rc == GF_ERR_ARG ? "bad pack: n, offsets (null or decreasing) or null reads" : "a read exceeds GF_MAX_READ_LEN");
+}
+
+// The batch route of one pack, queued on `st` into the staged arena `S`: the copy-in of its reads (`src`: the HOST's arrays;
+// ASCII too when a packed pack of nothing but empty reads came without pk) and offsets, the mapping call, the compaction.
+static int queue_batch(const gf_index* idx, hipStream_t st, const HostStage& S, const ReadSrc& src, const int64_t* offsets,
+                       const gf_pack_span& P, int64_t read_id_base, int64_t hits_cap) {
+  const int32_t maxlen = (int32_t)std::max<int64_t>(P.maxlen, 1);
+  const size_t off_bytes = ((size_t)P.n + 1) * sizeof(int64_t);
+  int rc;
+  if (src.packed()) {
+    const gf_packed_stage K = gf_packed_stage_for(P.b0, P.b1);
+    uint32_t* d_pk = (uint32_t*)S.bases;
+    uint16_t* d_iv = (uint16_t*)(S.bases + K.iv_at);
+    GF_HIP(hipMemcpyAsync(d_pk, src.pk + K.c0, (size_t)K.nc * 4, hipMemcpyHostToDevice, st));
+    GF_HIP(hipMemcpyAsync(d_iv, src.iv + K.c0, (size_t)K.nc * 2, hipMemcpyHostToDevice, st));
+    GF_HIP(hipMemcpyAsync(S.offsets, offsets, off_bytes, hipMemcpyHostToDevice, st));
+    // the device arrays start at chunk c0 of the host's stream
+    rc = gf_map_reads_packed_device(idx, d_pk - K.c0, d_iv - K.c0, S.offsets, P.n, maxlen, S.counts, S.matches, (void*)st);
+  } else {
+    // the 16-byte boundary at or below the first read is preserved (the kernels stage whole chunks)
+    const size_t lead = (size_t)((uintptr_t)(src.bases + P.b0) & 15u);
+    if (P.b1 > P.b0)
+      GF_HIP(hipMemcpyAsync(S.bases + lead, src.bases + P.b0, (size_t)(P.b1 - P.b0), hipMemcpyHostToDevice, st));
+    GF_HIP(hipMemcpyAsync(S.offsets, offsets, off_bytes, hipMemcpyHostToDevice, st));
+    // (S.bases + lead - b0) + offsets[r] = the device copy of read r
+    rc = gf_map_reads_device(idx, S.bases + lead - P.b0, S.offsets, P.n, maxlen, S.counts, S.matches, (void*)st);
   }
-  if (maxlen > GF_MAX_READ_LEN) return fail(GF_ERR_READ_TOO_LONG, "a read exceeds GF_MAX_READ_LEN");
-  const int64_t b0 = n > 0 ? offsets[0] : 0, b1 = n > 0 ? offsets[n] : 0;
-  if (b1 > b0 && !bases) return fail(GF_ERR_ARG, "bases is null");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t sz_bases = al((size_t)(b1 - b0) + 64), sz_off = al(((size_t)n + 1) * sizeof(int64_t));
-  const size_t sz_counts = al((size_t)n + 1), sz_matches = al(((size_t)n * 2 + 1) * sizeof(gf_seqmatch));
-  const size_t sz_hits = al(((size_t)hits_cap + 1) * sizeof(gf_hit)), sz_total = 256;
-  const size_t sz_cws = al((size_t)gf_compact_workspace_bytes(n) + 16);
-  int rc = lane_reserve(L, sz_bases + sz_off + sz_counts + sz_matches + sz_hits + sz_total + sz_cws);
   if (rc != GF_OK) return rc;
-  uint8_t* wp = (uint8_t*)L.arena;
-  uint8_t* d_bases = wp; wp += sz_bases;
-  S.offsets = (int64_t*)wp; wp += sz_off;
-  S.counts = wp; wp += sz_counts;
-  S.matches = (gf_seqmatch*)wp; wp += sz_matches;
-  S.hits = (gf_hit*)wp; wp += sz_hits;
-  S.total = (int64_t*)wp; wp += sz_total;
-  S.compact_ws = wp;
-  // the 16-byte boundary at or below the first read is preserved (the kernels stage whole chunks)
-  const size_t lead = (size_t)((uintptr_t)(bases + b0) & 15u);
-  S.bases = d_bases + lead - b0;  // S.bases + offsets[r] = the device copy of read r
-  if (n == 0) return GF_OK;
-  if (b1 > b0) GF_HIP(hipMemcpyAsync(d_bases + lead, bases + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, L.st));
-  GF_HIP(hipMemcpyAsync(S.offsets, offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, L.st));
-  return gf_map_reads_device(mix, S.bases, S.offsets, n, (int32_t)std::max<int64_t>(maxlen, 1), S.counts, S.matches,
-                             (void*)L.st);
+  return gf_compact_hits_device(idx, S.counts, S.matches, P.n, read_id_base, S.hits, hits_cap, S.total, S.compact_ws,
+                                (void*)st);
 }
 
 // Calls of a few reads — Indexer::map_read as the reference calls it, one read at a time — and calls of one PACK
@@ -1445,63 +1497,40 @@ static int stage_and_map(gf_index* mix, HostLane& L, const char* bases, const in
 // what a 2000-read call pays for (tools/bench_pack_sweep.py; DESIGN.md 4, "host calls").
 //   n <= GF_SMALL_CALL_READS (64):     one wave per read, probe-all kernel, a block per read
 //   n <= GF_PACK_CALL_READS:           the software-pipelined seed+verify kernel, grid-stride over the pack
-static int64_t small_call_reads() {
-  static const int64_t v = [] {
-    int64_t d = 64;
-    if (const char* e = getenv("GF_SMALL_CALL_READS")) d = std::max<int64_t>(0, atoll(e));
-    return d;
-  }();
-  return v;
-}
-#define GF_SMALL_CALL_READS small_call_reads()
-static int64_t pack_call_reads() {
-  static const int64_t v = [] {
-    int64_t d = 8192;  // (reads: packs of up to 4096 pairs; the crossover is measured by tools/bench_pack_sweep.py)
-    if (const char* e = getenv("GF_PACK_CALL_READS")) d = std::max<int64_t>(0, atoll(e));  // 0 = the batch route for every call beyond the small ones
-    return d;
-  }();
-  return v;
-}
+static int64_t reads_setting(const char* env, int64_t d) { return env ? std::max<int64_t>(0, atoll(env)) : d; }
+static int64_t small_call_reads() { static const int64_t v = reads_setting(getenv("GF_SMALL_CALL_READS"), 64); return v; }
+// (reads: packs of up to 4096 pairs; the crossover is measured by tools/bench_pack_sweep.py); 0 = the batch route for
+// every call beyond the small ones
+static int64_t pack_call_reads() { static const int64_t v = reads_setting(getenv("GF_PACK_CALL_READS"), 8192); return v; }
 static inline bool zero_copy_call(const gf_index* idx, int64_t n) {
   const int64_t lim = idx->pack_call_reads >= 0 ? idx->pack_call_reads : pack_call_reads();
-  return idx->map_variant == 0 && n > 0 && (n <= GF_SMALL_CALL_READS || n <= lim);
+  return idx->map_variant == 0 && n > 0 && (n <= small_call_reads() || n <= lim);
 }
 
-// validates the pack, stages it, queues its one launch on `st`
-static int zc_submit(gf_index* mix, ZeroCopy& Z, hipStream_t st, const char* bases, const int64_t* offsets, int64_t n) {
-  int64_t maxlen = 0;
-  for (int64_t r = 0; r < n; ++r) {
-    const int64_t l = offsets[r + 1] - offsets[r];
-    if (l < 0) return fail(GF_ERR_ARG, "offsets must be non-decreasing");
-    maxlen = std::max(maxlen, l);
-  }
-  if (maxlen > GF_MAX_READ_LEN) return fail(GF_ERR_READ_TOO_LONG, "a read exceeds GF_MAX_READ_LEN");
-  const int64_t b0 = offsets[0], b1 = offsets[n];
-  if (b1 > b0 && !bases) return fail(GF_ERR_ARG, "bases is null");
+// stages the (checked) pack, queues its one launch on `st`
+static int zc_submit(gf_index* mix, ZeroCopy& Z, hipStream_t st, const char* bases, const int64_t* offsets,
+                     const gf_pack_span& P) {
+  const int64_t n = P.n, b0 = P.b0, b1 = P.b1, maxlen = P.maxlen;
   // reads in a gf_host_alloc block are read where they are; anything else is staged in the pinned block
   const uint8_t* d_src = b1 > b0 ? pinned_device_address(bases + b0, (size_t)(b1 - b0)) : nullptr;
-  const size_t sz_flag = 64, sz_off = (((size_t)n + 1) * 8 + 15) & ~(size_t)15, sz_cnt = ((size_t)n + 15) & ~(size_t)15, sz_m = (size_t)n * 32;
-  const size_t sz_b = d_src ? 0 : (((size_t)(b1 - b0) + 64 + 15) & ~(size_t)15);
-  int rc = zc_reserve(Z, st, sz_flag + sz_off + sz_cnt + sz_m + sz_b + 64);
+  const gf_zc_layout zl = gf_zc_layout_for(n, b1 - b0, !d_src);
+  int rc = zc_reserve(Z, st, zl.bytes);
   if (rc != GF_OK) return rc;
-  int64_t* h_off = (int64_t*)(Z.pinned + sz_flag);
-  gf_seqmatch* h_m = (gf_seqmatch*)(Z.pinned + sz_flag + sz_off);
-  uint8_t* h_cnt = Z.pinned + sz_flag + sz_off + sz_m;
-  uint8_t* h_b = Z.pinned + sz_flag + sz_off + sz_m + sz_cnt;
+  uint8_t *const h = Z.pinned, *const d = Z.d_pinned;
+  int64_t* h_off = (int64_t*)(h + zl.offsets);
   for (int64_t r = 0; r <= n; ++r) h_off[r] = offsets[r] - b0;
-  if (!d_src && b1 > b0) memcpy(h_b, bases + b0, (size_t)(b1 - b0));
-  memset(h_cnt, 0, (size_t)n);  // (the kernels write the counts of the reads with segments only: GfTable::done_flag)
-  uint8_t* d = Z.d_pinned;
+  if (!d_src && b1 > b0) memcpy(h + zl.bases, bases + b0, (size_t)(b1 - b0));
+  memset(h + zl.counts, 0, (size_t)n);  // (the kernels write the counts of the reads with segments only: GfTable::done_flag)
   GfTable T = mix->table;
   Z.seq += 1;
   T.done_ctr = Z.d_done_ctr;
   T.done_flag = (unsigned int*)d;
   T.done_seq = Z.seq;
-  const uint8_t* d_b = d_src ? d_src : (const uint8_t*)(d + (h_b - Z.pinned));
-  const int64_t* d_off = (const int64_t*)(d + sz_flag);
-  uint8_t* d_cnt = d + (h_cnt - Z.pinned);
-  gf_seqmatch* d_m = (gf_seqmatch*)(d + sz_flag + sz_off);
-  if (n <= GF_SMALL_CALL_READS) {
+  const uint8_t* d_b = d_src ? d_src : (const uint8_t*)(d + zl.bases);
+  const int64_t* d_off = (const int64_t*)(d + zl.offsets);
+  uint8_t* d_cnt = d + zl.counts;
+  gf_seqmatch* d_m = (gf_seqmatch*)(d + zl.matches);
+  if (n <= small_call_reads()) {
     const int grid = (int)n;
     if (maxlen <= 256)
       hipLaunchKernelGGL((gf_k_map_reads<256, 1, 0>), dim3(grid), dim3(64), 0, st, T, d_b, d_off, n, -1, 1, d_cnt, d_m);
@@ -1514,8 +1543,8 @@ static int zc_submit(gf_index* mix, ZeroCopy& Z, hipStream_t st, const char* bas
     launch_wave_per_read(T, st, mix->n_cus, d_b, d_off, n, top, 1, d_cnt, d_m);
   }
   GF_HIP(hipGetLastError());
-  Z.h_counts = h_cnt;
-  Z.h_matches = h_m;
+  Z.h_counts = h + zl.counts;
+  Z.h_matches = (const gf_seqmatch*)(h + zl.matches);
   return GF_OK;
 }
 
@@ -1565,53 +1594,46 @@ static int64_t zc_hits(const ZeroCopy& Z, int64_t n, int64_t read_id_base, gf_hi
   return total;
 }
 
-static int map_small(gf_index* mix, HostLane& L, const char* bases, const int64_t* offsets, int64_t n,
-                     const uint8_t** out_counts, const gf_seqmatch** out_matches) {
-  int rc = zc_submit(mix, L.zc, L.st, bases, offsets, n);
-  if (rc != GF_OK) return rc;
-  rc = zc_wait(L.zc, L.st);
-  if (rc != GF_OK) return rc;
-  *out_counts = L.zc.h_counts;
-  *out_matches = L.zc.h_matches;
-  return GF_OK;
+// a zero-copy call on a lane, start to end: its counts and matches are then L.zc.h_counts / h_matches
+static int map_small(gf_index* mix, HostLane& L, const char* bases, const int64_t* offsets, const gf_pack_span& P) {
+  Drain drain{L.st, &L.zc};
+  int rc = zc_submit(mix, L.zc, L.st, bases, offsets, P);
+  if (rc == GF_OK) rc = zc_wait(L.zc, L.st);
+  drain.armed = rc != GF_OK;
+  return rc;
 }
 
 int gf_map_reads(const gf_index* idx, const char* bases, const int64_t* offsets, int64_t n,
                  int32_t* out_counts, gf_seqmatch* out_matches) {
   if (n > 0 && (!out_counts || !out_matches)) return fail(GF_ERR_ARG, "null output buffer");
   if (!idx) return fail(GF_ERR_ARG, "null index");
-  if (n < 0) return fail(GF_ERR_ARG, "negative n");
-  if (n > 0 && !offsets) return fail(GF_ERR_ARG, "offsets is null");
-  if (n == 0) return GF_OK;
+  gf_pack_span P;
+  int rc = pack_fail(gf_pack_measure(offsets, n, &P));
+  if (rc == GF_OK) rc = pack_fail(gf_pack_reads_present(P, bases != nullptr));
+  if (rc != GF_OK || n == 0) return rc;
   DeviceGuard guard(idx->device);
   gf_index* mix = const_cast<gf_index*>(idx);
   LaneLease lease(mix);
-  int rc = lease.acquire();
+  rc = lease.acquire();
   if (rc != GF_OK) return rc;
   HostLane& L = *lease.lane;
   if (zero_copy_call(idx, n)) {
-    const uint8_t* c8 = nullptr;
-    const gf_seqmatch* m = nullptr;
-    rc = map_small(mix, L, bases, offsets, n, &c8, &m);
+    rc = map_small(mix, L, bases, offsets, P);
     if (rc != GF_OK) return rc;
     for (int64_t r = 0; r < n; ++r) {
-      const int c = c8[r];
-      out_counts[r] = c;
-      for (int k = 0; k < c && k < 2; ++k) out_matches[2 * r + k] = m[2 * r + k];
+      const int c = out_counts[r] = L.zc.h_counts[r];
+      for (int k = 0; k < c && k < 2; ++k) out_matches[2 * r + k] = L.zc.h_matches[2 * r + k];
     }
     return GF_OK;
   }
   // the dense counts come back whole (a byte per read); of the matches only the reads that have
   // any (ordered compaction on the device): 48 bytes per hit instead of 32 per read
   const int64_t cap = std::max<int64_t>(1024, n / 16);
-  HostStage S;
-  // Whatever way this call ends, nothing may still be in flight on the lane when it does: the copies below land in
-  // local pageable buffers, and the lane goes back to the pool (an error between an asynchronous copy
-  // and its synchronisation left both dangling).
-  struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{L.st};
-  rc = stage_and_map(mix, L, bases, offsets, n, cap, S);
+  HostStage S{};
+  Drain drain{L.st};  // (never disarmed: the copies below land in local pageable buffers)
+  rc = lane_stage(L, P, cap, S);
   if (rc != GF_OK) return rc;
-  rc = gf_compact_hits_device(idx, S.counts, S.matches, n, 0, S.hits, cap, S.total, S.compact_ws, (void*)L.st);
+  rc = queue_batch(idx, L.st, S, ReadSrc{(const uint8_t*)bases}, offsets, P, 0, cap);
   if (rc != GF_OK) return rc;
   std::vector<uint8_t> c8((size_t)n);
   int64_t total = 0;
@@ -1653,27 +1675,26 @@ int gf_map_reads_hits(const gf_index* idx, const char* bases, const int64_t* off
   if (!out_n || cap < 0 || (cap > 0 && !out_hits)) return fail(GF_ERR_ARG, "bad output argument");
   if (!idx) return fail(GF_ERR_ARG, "null index");
   *out_n = 0;
+  gf_pack_span P;
+  int rc = pack_fail(gf_pack_measure(offsets, n, &P));
+  if (rc == GF_OK) rc = pack_fail(gf_pack_reads_present(P, bases != nullptr));
+  if (rc != GF_OK) return rc;
   DeviceGuard guard(idx->device);
   gf_index* mix = const_cast<gf_index*>(idx);
   LaneLease lease(mix);
-  int rc = lease.acquire();
+  rc = lease.acquire();
   if (rc != GF_OK) return rc;
   HostLane& L = *lease.lane;
-  if (n < 0) return fail(GF_ERR_ARG, "negative n");
-  if (n > 0 && !offsets) return fail(GF_ERR_ARG, "offsets is null");
   if (zero_copy_call(idx, n)) {  // one pack of the reference's size: one launch, the hit records put together here
-    const uint8_t* c8 = nullptr;
-    const gf_seqmatch* m = nullptr;
-    rc = map_small(mix, L, bases, offsets, n, &c8, &m);
-    if (rc != GF_OK) return rc;
-    *out_n = zc_hits(L.zc, n, read_id_base, out_hits, cap);
-    return GF_OK;
+    rc = map_small(mix, L, bases, offsets, P);
+    if (rc == GF_OK) *out_n = zc_hits(L.zc, n, read_id_base, out_hits, cap);
+    return rc;
   }
-  HostStage S;
-  struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{L.st};  // (see gf_map_reads)
-  rc = stage_and_map(mix, L, bases, offsets, n, cap, S);
+  HostStage S{};
+  Drain drain{L.st};  // (never disarmed: see gf_map_reads)
+  rc = lane_stage(L, P, cap, S);
   if (rc != GF_OK || n == 0) return rc;
-  rc = gf_compact_hits_device(idx, S.counts, S.matches, n, read_id_base, S.hits, cap, S.total, S.compact_ws, (void*)L.st);
+  rc = queue_batch(idx, L.st, S, ReadSrc{(const uint8_t*)bases}, offsets, P, read_id_base, cap);
   if (rc != GF_OK) return rc;
   int64_t total = 0;
   GF_HIP(hipMemcpyAsync(&total, S.total, sizeof total, hipMemcpyDeviceToHost, L.st));
@@ -1684,6 +1705,160 @@ int gf_map_reads_hits(const gf_index* idx, const char* bases, const int64_t* off
     GF_HIP(hipMemcpyAsync(out_hits, S.hits, (size_t)ncopy * sizeof(gf_hit), hipMemcpyDeviceToHost, L.st));
     GF_HIP(hipStreamSynchronize(L.st));
   }
+  return GF_OK;
+}
+
+// ---- streaming host entry: packs submitted ahead of the ones being mapped ---------------------
+// The consumer loop of the reference takes packs of reads off a queue while the producer keeps
+// reading the FASTQ (pescanner.rs:255-311).  Here a pack is SUBMITTED (copy in, mapping, compaction,
+// hit records out: all queued on the slot's own stream) and COLLECTED later; with `depth` slots the
+// copy of pack k+1 crosses the link while the kernels of pack k run and the hits of pack k-1 go back.
+struct gf_stream {
+  gf_index* ix = nullptr;
+  int depth = 0;
+  int64_t max_reads = 0, max_bytes = 0, pin_cap = 0;
+  struct Slot {
+    hipStream_t st = nullptr;
+    hipEvent_t done{};
+    uint8_t* arena = nullptr;  // device: the staged batch of (max_reads, max_bytes), hits_cap = max_reads
+    HostStage d{};             // its regions
+    gf_hit* h_hits = nullptr;  // pinned: the first pin_cap records of the pack
+    int64_t* h_total = nullptr;
+    ZeroCopy zc;               // a pack of up to GF_PACK_CALL_READS reads takes the zero-copy route (one launch, no copies)
+    // the pack it carries: set by stream_submit, read by gf_stream_collect
+    int64_t n = 0, read_id_base = 0;
+    bool zc_call = false;
+  };
+  std::vector<Slot> slots;
+  int head = 0, tail = 0, live = 0;
+  bool counted = false;  // registered in ix->open_streams
+};
+
+void gf_stream_close(gf_stream* s) {
+  if (!s) return;
+  DeviceGuard guard(s->ix->device);
+  if (s->counted) s->ix->open_streams.fetch_sub(1);
+  for (auto& sl : s->slots) {
+    if (sl.st) (void)hipStreamSynchronize(sl.st);
+    if (sl.arena) (void)hipFree(sl.arena);
+    if (sl.h_hits) (void)hipHostFree(sl.h_hits);
+    if (sl.h_total) (void)hipHostFree(sl.h_total);
+    sl.zc.release();
+    if (sl.st) {
+      (void)hipEventDestroy(sl.done);
+      // the mapping workspace cached for this stream goes with it
+      ws_pool(false).drop(s->ix->device, sl.st);
+      (void)hipStreamDestroy(sl.st);
+    }
+  }
+  delete s;
+}
+
+int gf_stream_open(const gf_index* idx, int64_t max_reads, int64_t max_bytes, int32_t depth, gf_stream** out) {
+  if (!out) return fail(GF_ERR_ARG, "out is null");
+  *out = nullptr;
+  if (!idx || max_reads <= 0 || max_bytes < 0 || depth < 1 || depth > 16) return fail(GF_ERR_ARG, "bad argument");
+  DeviceGuard guard(idx->device);
+  std::unique_ptr<gf_stream, void (*)(gf_stream*)> s(new gf_stream(), gf_stream_close);
+  s->ix = const_cast<gf_index*>(idx);
+  s->ix->open_streams.fetch_add(1);
+  s->counted = true;
+  s->depth = depth;
+  s->max_reads = max_reads;
+  s->max_bytes = max_bytes;
+  s->pin_cap = std::max<int64_t>(4096, max_reads / 16);
+  s->slots.resize((size_t)depth);
+  const gf_staged_layout a = gf_staged_layout_for(max_reads, max_bytes, max_reads, gf_compact_workspace_bytes(max_reads));
+  for (auto& sl : s->slots) {
+    GF_HIP(hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking));
+    GF_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    GF_HIP(hipMalloc((void**)&sl.arena, a.bytes));
+    sl.d = stage_at(sl.arena, a);
+    GF_HIP(hipHostMalloc((void**)&sl.h_hits, (size_t)s->pin_cap * sizeof(gf_hit), hipHostMallocDefault));
+    GF_HIP(hipHostMalloc((void**)&sl.h_total, 64, hipHostMallocDefault));
+  }
+  *out = s.release();
+  return GF_OK;
+}
+
+// One pack, ASCII or packed (`packed`: which entry was called, whatever `src` holds), into the slot at the head.  The
+// refusals come in the order they always had, the one check's halves among them.  Then the slot's per-pack state, HERE
+// for every kind of pack (a packed pack once inherited zc_call from the slot's last ASCII pack and was collected as that
+// one); the zero-copy launch, or the batch route and its read-back into the slot's pinned block; the slot in flight.
+static int stream_submit(gf_stream* s, const ReadSrc& src, bool packed, const int64_t* offsets, int64_t n, int64_t read_id_base) {
+  if (!s || n < 0 || (n > 0 && !offsets)) return fail(GF_ERR_ARG, "bad argument");
+  if (n > s->max_reads) return fail(GF_ERR_CAPACITY, "pack has more reads than the stream was opened for");
+  if (s->live == s->depth) return fail(GF_ERR_CAPACITY, "every slot is in flight: collect a pack first");
+  gf_pack_span P;
+  int rc = pack_fail(gf_pack_measure(offsets, n, &P));
+  if (rc != GF_OK) return rc;
+  if (packed && P.b0 < 0) return fail(GF_ERR_ARG, "negative offset");
+  if (P.b1 - P.b0 > s->max_bytes) return fail(GF_ERR_CAPACITY, "pack has more bases than the stream was opened for");
+  rc = pack_fail(gf_pack_reads_present(P, packed ? src.pk && src.iv : src.bases != nullptr));
+  if (rc != GF_OK) return rc;
+  if (packed && gf_packed_stage_for(P.b0, P.b1).bytes > (size_t)s->max_bytes + 64)
+    return fail(GF_ERR_CAPACITY, "pack has more bases than the stream was opened for");
+  DeviceGuard guard(s->ix->device);
+  gf_stream::Slot& sl = s->slots[(size_t)s->head];
+  sl.n = n;
+  sl.read_id_base = read_id_base;
+  sl.zc_call = !packed && zero_copy_call(s->ix, n);  // a pack of the reference's size: see ZeroCopy
+  // the pack becomes a slot in flight at the end or not at all: gf_stream_collect waits for it then
+  Drain drain{sl.st, sl.zc_call ? &sl.zc : nullptr};
+  if (sl.zc_call) {
+    rc = zc_submit(s->ix, sl.zc, sl.st, (const char*)src.bases, offsets, P);
+    if (rc != GF_OK) return rc;
+  } else {
+    *sl.h_total = 0;  // (what an empty pack leaves standing)
+    if (n > 0) {
+      rc = queue_batch(s->ix, sl.st, sl.d, src, offsets, P, read_id_base, n);
+      if (rc != GF_OK) return rc;
+      GF_HIP(hipMemcpyAsync(sl.h_total, sl.d.total, 8, hipMemcpyDeviceToHost, sl.st));
+      GF_HIP(hipMemcpyAsync(sl.h_hits, sl.d.hits, (size_t)std::min(n, s->pin_cap) * sizeof(gf_hit), hipMemcpyDeviceToHost, sl.st));
+    }
+    GF_HIP(hipEventRecord(sl.done, sl.st));
+  }
+  drain.armed = false;
+  s->head = (s->head + 1) % s->depth;
+  s->live += 1;
+  return GF_OK;
+}
+
+int gf_stream_submit(gf_stream* s, const char* bases, const int64_t* offsets, int64_t n, int64_t read_id_base) {
+  return stream_submit(s, ReadSrc{(const uint8_t*)bases}, false, offsets, n, read_id_base);
+}
+
+int gf_stream_submit_packed(gf_stream* s, const uint32_t* pk, const uint16_t* iv, const int64_t* offsets, int64_t n,
+                            int64_t read_id_base) {
+  return stream_submit(s, ReadSrc{nullptr, pk, iv}, true, offsets, n, read_id_base);
+}
+
+int gf_stream_collect(gf_stream* s, gf_hit* out_hits, int64_t cap, int64_t* out_n) {
+  if (!s || !out_n || cap < 0 || (cap > 0 && !out_hits)) return fail(GF_ERR_ARG, "bad argument");
+  *out_n = 0;
+  if (s->live == 0) return fail(GF_ERR_ARG, "no pack in flight");
+  DeviceGuard guard(s->ix->device);
+  gf_stream::Slot& sl = s->slots[(size_t)s->tail];
+  if (sl.zc_call) {
+    // (a pack that fails here stays the oldest in flight, with nothing of it left running: every later collect waits
+    // for it and fails again, so all that is left to do with the stream is to close it)
+    Drain drain{sl.st, &sl.zc};
+    const int rc = zc_wait(sl.zc, sl.st);
+    if (rc != GF_OK) return rc;
+    drain.armed = false;
+    *out_n = zc_hits(sl.zc, sl.n, sl.read_id_base, out_hits, cap);
+  } else {
+    GF_HIP(hipEventSynchronize(sl.done));
+    *out_n = *sl.h_total;  // (0 for an empty pack)
+    const int64_t want = std::min(*out_n, cap);
+    const int64_t from_pin = std::min(want, std::min(sl.n, s->pin_cap));
+    if (from_pin > 0) memcpy(out_hits, sl.h_hits, (size_t)from_pin * sizeof(gf_hit));
+    if (want > from_pin)  // more hits than the pinned block holds: the rest straight from the device list
+      GF_HIP(hipMemcpy(out_hits + from_pin, sl.d.hits + from_pin, (size_t)(want - from_pin) * sizeof(gf_hit),
+                       hipMemcpyDeviceToHost));
+  }
+  s->tail = (s->tail + 1) % s->depth;
+  s->live -= 1;
   return GF_OK;
 }
 
@@ -2359,266 +2534,12 @@ int gf_scan_pairs_text_device(const gf_index* idx, const void* d_l_bases, const 
                          d_totals, stream, d_l_qual_off, d_r_qual_off);
 }
 
-// ---- streaming host entry: packs submitted ahead of the ones being mapped ---------------------
-// The consumer loop of the reference takes packs of reads off a queue while the producer keeps
-// reading the FASTQ (pescanner.rs:255-311).  Here a pack is SUBMITTED (copy in, mapping, compaction,
-// hit records out: all queued on the slot's own stream) and COLLECTED later; with `depth` slots the
-// copy of pack k+1 crosses the link while the kernels of pack k run and the hits of pack k-1 go back.
-struct gf_stream {
-  gf_index* ix = nullptr;
-  int depth = 0;
-  int64_t max_reads = 0, max_bytes = 0, pin_cap = 0;
-  struct Slot {
-    hipStream_t st = nullptr;
-    hipEvent_t done{};
-    uint8_t* arena = nullptr;  // device: bases | offsets | counts | matches | hits | total | compaction workspace
-    uint8_t* d_bases = nullptr; int64_t* d_off = nullptr; uint8_t* d_counts = nullptr; gf_seqmatch* d_matches = nullptr;
-    gf_hit* d_hits = nullptr; int64_t* d_total = nullptr; uint8_t* d_cws = nullptr;
-    gf_hit* h_hits = nullptr;  // pinned: the first pin_cap records of the pack
-    int64_t* h_total = nullptr;
-    bool inflight = false;
-    int64_t n = 0;
-    ZeroCopy zc;              // a pack of up to GF_PACK_CALL_READS reads takes the zero-copy route (one launch, no copies)
-    bool zc_call = false;
-    int64_t read_id_base = 0;
-  };
-  std::vector<Slot> slots;
-  int head = 0, tail = 0, live = 0;
-  bool counted = false;  // registered in ix->open_streams
-};
-
 int gf_copy_from_host_device(const gf_index* idx, const void* h_src, void* d_dst, int64_t nbytes, void* stream) {
   if (!idx || nbytes < 0) return fail(GF_ERR_ARG, "null index or negative size");
   if (nbytes == 0) return GF_OK;
   if (!h_src || !d_dst) return fail(GF_ERR_ARG, "null pointer");
   DeviceGuard guard(idx->device);
   GF_HIP(hipMemcpyAsync(d_dst, h_src, (size_t)nbytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-  return GF_OK;
-}
-
-void* gf_host_alloc(int64_t bytes) {
-  if (bytes <= 0) return nullptr;
-  void* p = nullptr;
-  if (hipHostMalloc(&p, (size_t)bytes, hipHostMallocDefault) != hipSuccess) {
-    g_err = "hipHostMalloc failed";
-    return nullptr;
-  }
-  void* d = nullptr;
-  if (hipHostGetDevicePointer(&d, p, 0) == hipSuccess && d) {  // known to the zero-copy calls: they read it in place
-    std::unique_lock<std::shared_mutex> lk(g_pinned_mu);
-    g_pinned.push_back({(const char*)p, (size_t)bytes, (const uint8_t*)d});
-  } else {
-    (void)hipGetLastError();
-  }
-  return p;
-}
-
-void gf_host_free(void* p) {
-  if (!p) return;
-  {
-    std::unique_lock<std::shared_mutex> lk(g_pinned_mu);
-    for (size_t i = 0; i < g_pinned.size(); ++i)
-      if (g_pinned[i].host == (const char*)p) {
-        g_pinned.erase(g_pinned.begin() + (long)i);
-        break;
-      }
-  }
-  (void)hipHostFree(p);
-}
-
-void gf_stream_close(gf_stream* s) {
-  if (!s) return;
-  DeviceGuard guard(s->ix->device);
-  if (s->counted) s->ix->open_streams.fetch_sub(1);
-  for (auto& sl : s->slots) {
-    if (sl.st) (void)hipStreamSynchronize(sl.st);
-    if (sl.arena) (void)hipFree(sl.arena);
-    if (sl.h_hits) (void)hipHostFree(sl.h_hits);
-    if (sl.h_total) (void)hipHostFree(sl.h_total);
-    sl.zc.release();
-    if (sl.st) {
-      (void)hipEventDestroy(sl.done);
-      // the mapping workspace cached for this stream goes with it
-      ws_pool(false).drop(s->ix->device, sl.st);
-      (void)hipStreamDestroy(sl.st);
-    }
-  }
-  delete s;
-}
-
-int gf_stream_open(const gf_index* idx, int64_t max_reads, int64_t max_bytes, int32_t depth, gf_stream** out) {
-  if (!out) return fail(GF_ERR_ARG, "out is null");
-  *out = nullptr;
-  if (!idx || max_reads <= 0 || max_bytes < 0 || depth < 1 || depth > 16) return fail(GF_ERR_ARG, "bad argument");
-  DeviceGuard guard(idx->device);
-  std::unique_ptr<gf_stream, void (*)(gf_stream*)> s(new gf_stream(), gf_stream_close);
-  s->ix = const_cast<gf_index*>(idx);
-  s->ix->open_streams.fetch_add(1);
-  s->counted = true;
-  s->depth = depth;
-  s->max_reads = max_reads;
-  s->max_bytes = max_bytes;
-  s->pin_cap = std::max<int64_t>(4096, max_reads / 16);
-  s->slots.resize((size_t)depth);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t sz_b = al((size_t)max_bytes + 64), sz_o = al(((size_t)max_reads + 1) * 8), sz_c = al((size_t)max_reads + 1);
-  const size_t sz_m = al(((size_t)max_reads * 2 + 1) * sizeof(gf_seqmatch)), sz_h = al(((size_t)max_reads + 1) * sizeof(gf_hit));
-  const size_t sz_w = al((size_t)gf_compact_workspace_bytes(max_reads) + 16);
-  for (auto& sl : s->slots) {
-    GF_HIP(hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking));
-    GF_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    GF_HIP(hipMalloc((void**)&sl.arena, sz_b + sz_o + sz_c + sz_m + sz_h + 256 + sz_w));
-    uint8_t* wp = sl.arena;
-    sl.d_bases = wp; wp += sz_b;
-    sl.d_off = (int64_t*)wp; wp += sz_o;
-    sl.d_counts = wp; wp += sz_c;
-    sl.d_matches = (gf_seqmatch*)wp; wp += sz_m;
-    sl.d_hits = (gf_hit*)wp; wp += sz_h;
-    sl.d_total = (int64_t*)wp; wp += 256;
-    sl.d_cws = wp;
-    GF_HIP(hipHostMalloc((void**)&sl.h_hits, (size_t)s->pin_cap * sizeof(gf_hit), hipHostMallocDefault));
-    GF_HIP(hipHostMalloc((void**)&sl.h_total, 64, hipHostMallocDefault));
-  }
-  *out = s.release();
-  return GF_OK;
-}
-
-int gf_stream_submit(gf_stream* s, const char* bases, const int64_t* offsets, int64_t n, int64_t read_id_base) {
-  if (!s || n < 0 || (n > 0 && !offsets)) return fail(GF_ERR_ARG, "bad argument");
-  if (n > s->max_reads) return fail(GF_ERR_CAPACITY, "pack has more reads than the stream was opened for");
-  if (s->live == s->depth) return fail(GF_ERR_CAPACITY, "every slot is in flight: collect a pack first");
-  int64_t maxlen = 0;
-  for (int64_t r = 0; r < n; ++r) {
-    const int64_t l = offsets[r + 1] - offsets[r];
-    if (l < 0) return fail(GF_ERR_ARG, "offsets must be non-decreasing");
-    maxlen = std::max(maxlen, l);
-  }
-  if (maxlen > GF_MAX_READ_LEN) return fail(GF_ERR_READ_TOO_LONG, "a read exceeds GF_MAX_READ_LEN");
-  const int64_t b0 = n > 0 ? offsets[0] : 0, b1 = n > 0 ? offsets[n] : 0;
-  if (b1 - b0 > s->max_bytes) return fail(GF_ERR_CAPACITY, "pack has more bytes than the stream was opened for");
-  if (b1 > b0 && !bases) return fail(GF_ERR_ARG, "bases is null");
-  DeviceGuard guard(s->ix->device);
-  gf_stream::Slot& sl = s->slots[(size_t)s->head];
-  sl.n = n;
-  sl.zc_call = false;
-  sl.read_id_base = read_id_base;
-  if (zero_copy_call(s->ix, n)) {  // a pack of the reference's size: see ZeroCopy
-    const int rc = zc_submit(s->ix, sl.zc, sl.st, bases, offsets, n);
-    if (rc != GF_OK) return rc;
-    sl.zc_call = true;
-    sl.inflight = true;
-    s->head = (s->head + 1) % s->depth;
-    s->live += 1;
-    return GF_OK;
-  }
-  if (n > 0) {
-    const size_t lead = (size_t)((uintptr_t)(bases + b0) & 15u);  // keep the span's 16-byte phase
-    struct Drain { hipStream_t st; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(st); } } drain{sl.st};  // (see gf_stream_submit_packed)
-    if (b1 > b0) GF_HIP(hipMemcpyAsync(sl.d_bases + lead, bases + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, sl.st));
-    GF_HIP(hipMemcpyAsync(sl.d_off, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, sl.st));
-    int rc = gf_map_reads_device(s->ix, sl.d_bases + lead - b0, sl.d_off, n, (int32_t)std::max<int64_t>(maxlen, 1),
-                                 sl.d_counts, sl.d_matches, (void*)sl.st);
-    if (rc != GF_OK) return rc;
-    rc = gf_compact_hits_device(s->ix, sl.d_counts, sl.d_matches, n, read_id_base, sl.d_hits, n, sl.d_total, sl.d_cws,
-                                (void*)sl.st);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipMemcpyAsync(sl.h_total, sl.d_total, 8, hipMemcpyDeviceToHost, sl.st));
-    GF_HIP(hipMemcpyAsync(sl.h_hits, sl.d_hits, (size_t)std::min(n, s->pin_cap) * sizeof(gf_hit), hipMemcpyDeviceToHost,
-                          sl.st));
-    drain.armed = false;
-  } else {
-    *sl.h_total = 0;
-  }
-  GF_HIP(hipEventRecord(sl.done, sl.st));
-  sl.inflight = true;
-  s->head = (s->head + 1) % s->depth;
-  s->live += 1;
-  return GF_OK;
-}
-
-int gf_stream_submit_packed(gf_stream* s, const uint32_t* pk, const uint16_t* iv, const int64_t* offsets, int64_t n,
-                            int64_t read_id_base) {
-  if (!s || n < 0 || (n > 0 && !offsets)) return fail(GF_ERR_ARG, "bad argument");
-  if (n > s->max_reads) return fail(GF_ERR_CAPACITY, "pack has more reads than the stream was opened for");
-  if (s->live == s->depth) return fail(GF_ERR_CAPACITY, "every slot is in flight: collect a pack first");
-  int64_t maxlen = 0;
-  for (int64_t r = 0; r < n; ++r) {
-    const int64_t l = offsets[r + 1] - offsets[r];
-    if (l < 0) return fail(GF_ERR_ARG, "offsets must be non-decreasing");
-    maxlen = std::max(maxlen, l);
-  }
-  if (maxlen > GF_MAX_READ_LEN) return fail(GF_ERR_READ_TOO_LONG, "a read exceeds GF_MAX_READ_LEN");
-  const int64_t b0 = n > 0 ? offsets[0] : 0, b1 = n > 0 ? offsets[n] : 0;
-  if (b0 < 0) return fail(GF_ERR_ARG, "negative offset");
-  if (b1 - b0 > s->max_bytes) return fail(GF_ERR_CAPACITY, "pack has more bases than the stream was opened for");
-  if (b1 > b0 && (!pk || !iv)) return fail(GF_ERR_ARG, "null packed stream");
-  DeviceGuard guard(s->ix->device);
-  gf_stream::Slot& sl = s->slots[(size_t)s->head];
-  sl.n = n;
-  if (n > 0) {
-    // chunks c0 .. c1-1 cover the pack's bases and the four chunks past them that every packed buffer carries
-    // (gf_packed_chunks: the kernels' staging reads past a tile's last chunk; the host's arrays hold them — the next
-    // reads' chunks inside a buffer, gf_pack_bases_host's padding at its end); the slot's base area
-    // (max_bytes + 64 bytes) holds them: 6 bytes per chunk of 16 bases
-    const int64_t c0 = b0 >> 4, c1 = ((b1 + 15) >> 4) + 4, nc = c1 - c0;
-    uint32_t* d_pk = (uint32_t*)sl.d_bases;
-    uint16_t* d_iv = (uint16_t*)(sl.d_bases + (((size_t)nc * 4 + 15) & ~(size_t)15));
-    if ((((size_t)nc * 4 + 15) & ~(size_t)15) + (size_t)nc * 2 > (size_t)s->max_bytes + 64)
-      return fail(GF_ERR_CAPACITY, "pack has more bases than the stream was opened for");
-    // whatever way this call ends, the copies out of the caller's pinned pk / iv / offsets are not left pending on
-    // an error return (the caller may reuse them at once: the pack never became a slot in flight)
-    struct Drain { hipStream_t st; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(st); } } drain{sl.st};
-    GF_HIP(hipMemcpyAsync(d_pk, pk + c0, (size_t)nc * 4, hipMemcpyHostToDevice, sl.st));
-    GF_HIP(hipMemcpyAsync(d_iv, iv + c0, (size_t)nc * 2, hipMemcpyHostToDevice, sl.st));
-    GF_HIP(hipMemcpyAsync(sl.d_off, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, sl.st));
-    // the device arrays start at chunk c0 of the host's stream: shift the pointers, the offsets stay as they are
-    int rc = gf_map_reads_packed_device(s->ix, d_pk - c0, d_iv - c0, sl.d_off, n, (int32_t)std::max<int64_t>(maxlen, 1),
-                                        sl.d_counts, sl.d_matches, (void*)sl.st);
-    if (rc != GF_OK) return rc;
-    rc = gf_compact_hits_device(s->ix, sl.d_counts, sl.d_matches, n, read_id_base, sl.d_hits, n, sl.d_total, sl.d_cws,
-                                (void*)sl.st);
-    if (rc != GF_OK) return rc;
-    GF_HIP(hipMemcpyAsync(sl.h_total, sl.d_total, 8, hipMemcpyDeviceToHost, sl.st));
-    GF_HIP(hipMemcpyAsync(sl.h_hits, sl.d_hits, (size_t)std::min(n, s->pin_cap) * sizeof(gf_hit), hipMemcpyDeviceToHost,
-                          sl.st));
-    drain.armed = false;  // the pack is in flight: gf_stream_collect waits for it
-  } else {
-    *sl.h_total = 0;
-  }
-  GF_HIP(hipEventRecord(sl.done, sl.st));
-  sl.inflight = true;
-  s->head = (s->head + 1) % s->depth;
-  s->live += 1;
-  return GF_OK;
-}
-
-int gf_stream_collect(gf_stream* s, gf_hit* out_hits, int64_t cap, int64_t* out_n) {
-  if (!s || !out_n || cap < 0 || (cap > 0 && !out_hits)) return fail(GF_ERR_ARG, "bad argument");
-  *out_n = 0;
-  if (s->live == 0) return fail(GF_ERR_ARG, "no pack in flight");
-  DeviceGuard guard(s->ix->device);
-  gf_stream::Slot& sl = s->slots[(size_t)s->tail];
-  if (sl.zc_call) {
-    const int rc = zc_wait(sl.zc, sl.st);
-    if (rc != GF_OK) return rc;
-    *out_n = zc_hits(sl.zc, sl.n, sl.read_id_base, out_hits, cap);
-    sl.inflight = false;
-    s->tail = (s->tail + 1) % s->depth;
-    s->live -= 1;
-    return GF_OK;
-  }
-  GF_HIP(hipEventSynchronize(sl.done));
-  const int64_t total = sl.n > 0 ? *sl.h_total : 0;
-  *out_n = total;
-  const int64_t want = std::min(total, cap);
-  const int64_t from_pin = std::min(want, std::min(sl.n, s->pin_cap));
-  if (from_pin > 0) memcpy(out_hits, sl.h_hits, (size_t)from_pin * sizeof(gf_hit));
-  if (want > from_pin)  // more hits than the pinned block holds: the rest straight from the device list
-    GF_HIP(hipMemcpy(out_hits + from_pin, sl.d_hits + from_pin, (size_t)(want - from_pin) * sizeof(gf_hit),
-                     hipMemcpyDeviceToHost));
-  sl.inflight = false;
-  s->tail = (s->tail + 1) % s->depth;
-  s->live -= 1;
   return GF_OK;
 }
 
