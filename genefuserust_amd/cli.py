@@ -5,7 +5,7 @@ The options of the reference (src/argparse.rs) keep their letters and defaults â
 the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired or single-end), the HTML report and
 the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
 out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, the
-whole-genome alignable filter, and the quality filter of the reads ahead of the scan.
+whole-genome alignable filter, and the adapter trimming and the quality filter of the reads ahead of the scan.
 """
 from __future__ import annotations
 
@@ -74,6 +74,20 @@ def parser() -> argparse.ArgumentParser:
     rf.add_argument("--cut-tail-mean", type=int, default=None, help="the mean phred a tail window must reach, default 20")
     rf.add_argument("--poly-g-min", type=int, default=None, help="cut off a poly-G tail of at least this many bases, "
                     "default 10; 0: off")
+    at = p.add_argument_group("adapter trimming (off by default; any of its options switches it on)")
+    at.add_argument("--trim-adapters", action="store_true", help="cut the reads to the insert on the device ahead of "
+                    "the read filter and the scan: pairs by the overlap of their mates, with the defaults below")
+    at.add_argument("--adapter-r1", default=None, help="the adapter behind read1's insert, looked for in reads that "
+                    "no overlap cut (and in single-end reads, which need it): 4 to 64 bases of ACGT, or illumina")
+    at.add_argument("--adapter-r2", default=None, help="the adapter behind read2's insert, as --adapter-r1")
+    at.add_argument("--adapter-min-overlap", type=int, default=None, help="the fewest positions an overlap compares, "
+                    "default 30")
+    at.add_argument("--adapter-max-diff", type=int, default=None, help="the most differences inside an overlap, "
+                    "default 5")
+    at.add_argument("--adapter-diff-percent", type=int, default=None, help="the share of differences inside an "
+                    "overlap, default 20")
+    at.add_argument("--adapter-min-match", type=int, default=None, help="the fewest adapter bases looked for at a "
+                    "read's end, default 10")
     return p
 
 
@@ -89,6 +103,22 @@ def _read_filter(args):
         return None
     from .read_filter import ReadFilter
     return ReadFilter(**given)
+
+
+# option -> the field of ``AdapterTrim`` it sets
+ADAPTER_TRIM_OPTIONS = {"adapter_r1": "adapter_r1", "adapter_r2": "adapter_r2", "adapter_min_overlap": "min_overlap",
+                        "adapter_max_diff": "max_diff", "adapter_diff_percent": "diff_percent",
+                        "adapter_min_match": "min_adapter"}
+
+
+def _adapter_trim(args):
+    """The ``AdapterTrim`` the options ask for, None when none of them is given; ``ValueError`` for a value out of
+    range."""
+    given = {f: getattr(args, k) for k, f in ADAPTER_TRIM_OPTIONS.items() if getattr(args, k) is not None}
+    if not (args.trim_adapters or given):
+        return None
+    from .adapter_trim import AdapterTrim
+    return AdapterTrim(**given)
 
 
 def _missing(args) -> Optional[str]:
@@ -121,6 +151,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         read_filter = _read_filter(args)
         if read_filter is not None:   # (off: the calls of today)
             common["read_filter"] = read_filter
+        adapter_trim = _adapter_trim(args)
+        if adapter_trim is not None:
+            common["adapter_trim"] = adapter_trim
         if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")

@@ -158,7 +158,7 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
 def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host",
-                      originals: bool = False, *, read_filter=None):
+                      originals: bool = False, *, read_filter=None, adapter_trim=None):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
@@ -169,8 +169,11 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     ``originals``: the FASTQ records of each index's hit records are gathered behind its scan too and fetched per index,
     beside the block (whose format stays): a read-back or two more per index and chunk.  ``read_filter``: a
     ``ReadFilter``, every chunk's records go through the read filter once, ahead of the pairs' preparation
-    (``scan_stream._scan_chunk``); every index reports the same filter totals, in front of its filter counts."""
+    (``scan_stream._scan_chunk``); every index reports the same filter totals, in front of its filter counts.
+    ``adapter_trim``: an ``AdapterTrim``, the same for the adapter trimming ahead of the read filter; its totals stand in
+    front of the read filter's."""
     from . import scan_pack, scan_stream
+    from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
     from .fusion_mapper import FusionMapper
     from .read_pair import finish_pair_hits
@@ -181,9 +184,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     mappers = [FusionMapper(ix) for ix in indexers]
     found = [[] for _ in indexers]
     sums = [{count_key: 0, "merged_pairs": 0, "retried_reads": 0} for _ in indexers]
-    if read_filter is not None:
-        for t in sums:
-            t.update(dict.fromkeys(COUNTER_KEYS, 0))
+    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS)
+    for t in sums:
+        t.update(dict.fromkeys(extra, 0))
     chunks = 0
 
     def scan_records(ix0, texts, batches, m, done, max_read_len, names):
@@ -224,7 +227,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
         sources = scan_stream.open_fastq_sources(opened, files, inflate)
         for per_index in scan_stream._scan_source_stream(indexers[0], sources, chunk_bytes, None, True, scan_records,
                                                          lean=False, **({} if read_filter is None else
-                                                                        {"read_filter": read_filter})):
+                                                                        {"read_filter": read_filter}),
+                                                         **({} if adapter_trim is None else
+                                                            {"adapter_trim": adapter_trim})):
             for k, (rec, hb, hq, names, tot, *orig) in enumerate(per_index):
                 found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names, *orig)
                 for key in sums[k]:
@@ -233,8 +238,7 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     out = []
     for f, t in zip(found, sums):
         before, after = route_counters(count_key, t[count_key], len(f), t, chunks)
-        if read_filter is not None:
-            before.update({k: t[k] for k in COUNTER_KEYS})
+        before.update({k: t[k] for k in extra})
         out.append((f, before, after))
     return out
 
@@ -243,7 +247,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                           settings: Settings = None, json_file: str = "", command: str = "", version: str = "",
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
                           hits_cap: int = None, inflate: str = "host", tail: str = "host", originals: bool = False,
-                          html_file: str = "", *, read_filter=None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          html_file: str = "", *, read_filter=None,
+                          adapter_trim=None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -273,16 +278,23 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
     ``read_filter``: None or a ``read_filter.ReadFilter``, the quality filter ahead of the scan
     (``scan.scan_pair_end_files``).  It runs once — over the resident records, or once per chunk — ahead of
-    ``prepare_pairs_device``, and every CSV reports the same seven filter totals."""
+    ``prepare_pairs_device``, and every CSV reports the same seven filter totals.
+
+    ``adapter_trim``: None or an ``adapter_trim.AdapterTrim``, adapter trimming ahead of the read filter
+    (``scan.scan_pair_end_files``), once as well; every CSV reports the same five totals.  Without ``read2_file`` it
+    needs ``adapter_r1``."""
+    from .adapter_trim import need_adapter_trim
     from .fastq import FastqReader, FastqReaderPair
     from .read_filter import need_read_filter
     from .report_tail import need_tail
     need_tail(tail)
     need_read_filter(read_filter)
+    if need_adapter_trim(adapter_trim) is not None and not read2_file and not adapter_trim.adapter_r1:
+        raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     from .fusion_mapper import FusionMapper
     from .indexer import Fusion
     from .scan import (GeneSlices, _route_inflate, filtered_reads, finish_matches, open_index, pairs_found,
-                       read_contigs, report_matches, single_end_found)
+                       read_contigs, report_matches, single_end_found, trimmed_reads)
     settings = settings or Settings()
     fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
     csvs = read_csv_list(csv_list_file)
@@ -306,7 +318,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
             opened = [stack.enter_context(open_index(refs[k], csv, device)) for k, csv in enumerate(csvs)]
             files = (read1_file, read2_file) if read2_file else (read1_file,)
             produced = (_stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap, fq_inflate, originals,
-                                          **({} if read_filter is None else {"read_filter": read_filter}))
+                                          **({} if read_filter is None else {"read_filter": read_filter}),
+                                          **({} if adapter_trim is None else {"adapter_trim": adapter_trim}))
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
@@ -315,18 +328,20 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
         for k, (_, results, _) in enumerate(out):
             write(k, results)
         return out
-    reads = prepared = counted = None
+    reads = prepared = counted = trimmed = None
     for k, csv in enumerate(csvs):
         with open_index(refs[k], csv, device) as (ix, fusions):
             if reads is None:   # (the first index names the device the records go to)
                 if read2_file:
                     (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
+                    (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
                     (l, r), counted = filtered_reads(ix, read_filter, l, r)
                     reads = (l, ltext), (r, rtext)
                     prepared = prepare_pairs_device(ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets,
                                                     max(l.max_read_len(), r.max_read_len(), 1))
                 else:
                     b, text = FastqReader(read1_file).read_all_device(ix)
+                    (b,), trimmed = trimmed_reads(ix, adapter_trim, b)
                     (b,), counted = filtered_reads(ix, read_filter, b)
                     reads = b, text
             mapper = FusionMapper(ix)
@@ -335,7 +350,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                        lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps), originals)
             else:
                 produced = single_end_found(ix, mapper, *reads, originals)
-            produced = counted(produced)
+            produced = counted(trimmed(produced))
             kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:],
                                             tail=tail)
             results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)
@@ -348,7 +363,7 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
                 chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
                 originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False, *,
-                alignable_filter: str = None, read_filter=None):
+                alignable_filter: str = None, read_filter=None, adapter_trim=None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -363,11 +378,15 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     ``ValueError`` in the other modes, which do not have it.  ``alignable_filter``: None or "genome", the whole-genome
     alignable filter on the device of the single-CSV scanners (``scan.scan_pair_end_files``); ``ValueError`` for a list
     of CSVs.  ``read_filter``: None or a ``read_filter.ReadFilter``, the quality filter ahead of the scan, in every
-    mode (``scan.scan_pair_end_files``); it is handed on only when set."""
+    mode (``scan.scan_pair_end_files``); it is handed on only when set.  ``adapter_trim``: None or an
+    ``adapter_trim.AdapterTrim``, adapter trimming ahead of the read filter, in every mode, handed on only when set."""
     from . import scan
+    from .adapter_trim import need_adapter_trim
     from .alignable import need_filter
     from .read_filter import need_read_filter
     filtered = {} if need_read_filter(read_filter) is None else {"read_filter": read_filter}
+    if need_adapter_trim(adapter_trim) is not None:
+        filtered["adapter_trim"] = adapter_trim
     if need_filter(alignable_filter, remove_alignables) and _rust_stem_ext(fusion_file)[2] != "csv":
         raise ValueError("alignable_filter: only the scans of one CSV have this filter")
     if remove_alignables and not (_rust_stem_ext(fusion_file)[2] == "csv" and read2_file):

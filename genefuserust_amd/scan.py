@@ -127,6 +127,23 @@ def filtered_reads(ix: Indexer, read_filter, *batches):
     return tuple(kept), counted
 
 
+def trimmed_reads(ix: Indexer, adapter_trim, *batches):
+    """The ``FastqBatch``es (a file's records, or a pair's) through the adapter trimming on the index's device
+    (adapter_trim.py), ahead of ``filtered_reads``: (the batches it leaves, ``counted(produced)``).  ``counted`` adds the
+    trimming's five totals to the end of a producer's counters in front of the filter counts — so it is applied before
+    ``filtered_reads``' — and ``adapter_trim`` None gives the batches as they are, nothing queued, and a ``counted``
+    that changes nothing."""
+    if adapter_trim is None:
+        return batches, lambda produced: produced
+    from .adapter_trim import adapter_totals_counters, trim_adapters_device
+    *kept, totals = trim_adapters_device(ix, adapter_trim, *batches)
+
+    def counted(produced):
+        found, before, after = produced
+        return found, {**before, **adapter_totals_counters(totals.cpu().tolist())}, after
+    return tuple(kept), counted
+
+
 def finish_matches(found: List[ReadMatch], mapper, deletion_threshold: int, remove_alignables: bool, before: dict,
                    after: dict, tail: str = "host", *, alignable_filter: str = None) -> Tuple[List[ReadMatch], dict]:
     """The tail of every route: the filters, (matches kept in ``sort_matches`` order, counters).  ``tail``: "host", a
@@ -212,35 +229,39 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
 
 
 def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
-                   originals: bool = False, *, read_filter=None) -> Tuple[List[ReadMatch], dict, dict]:
+                   originals: bool = False, *, read_filter=None,
+                   adapter_trim=None) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
     order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
     ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``).
     ``read_filter``: a ``ReadFilter``, every chunk's records go through the read filter ahead of the scan
     (``scan_stream._scan_chunk``) and its totals, summed over the chunks, end the counters in front of the filter
-    counts."""
+    counts.  ``adapter_trim``: an ``AdapterTrim``, every chunk's records go through the adapter trimming ahead of that,
+    and its five totals stand in front of the read filter's."""
+    from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
     from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
     count_key = "pairs" if len(files) == 2 else "reads"
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
     found: List[ReadMatch] = []
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
-    if read_filter is not None:
-        sums.update(dict.fromkeys(COUNTER_KEYS, 0))
+    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS)
+    sums.update(dict.fromkeys(extra, 0))
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        # (originals=False and read_filter=None are not passed on: the stream is then called as it always was)
+        # (originals=False, read_filter=None and adapter_trim=None are not passed on: the stream is then called as it
+        #  always was)
         for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
                                                      **({"originals": True} if originals else {}),
-                                                     **({"read_filter": read_filter} if read_filter is not None else {})):
+                                                     **({"read_filter": read_filter} if read_filter is not None else {}),
+                                                     **({"adapter_trim": adapter_trim} if adapter_trim is not None else {})):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
             chunks += 1
     before, after = route_counters(count_key, sums[count_key], len(found), sums, chunks)
-    if read_filter is not None:
-        before.update({k: sums[k] for k in COUNTER_KEYS})
+    before.update({k: sums[k] for k in extra})
     return found, before, after
 
 
@@ -263,12 +284,14 @@ def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) ->
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
                       chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
-                      alignable_filter=None, read_filter=None):
+                      alignable_filter=None, read_filter=None, adapter_trim=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
+    from .adapter_trim import need_adapter_trim
     from .read_filter import need_read_filter
     from .report_tail import need_tail
     need_tail(tail)
     need_read_filter(read_filter)
+    need_adapter_trim(adapter_trim)
     _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
@@ -278,15 +301,17 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
             produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate, originals,
-                                      **({"read_filter": read_filter} if read_filter is not None else {}))
+                                      **({"read_filter": read_filter} if read_filter is not None else {}),
+                                      **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}))
         else:
             (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
+            (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
             (l, r), counted = filtered_reads(ix, read_filter, l, r)
             reads = (l, ltext), (r, rtext)
             max_len = max(l.max_read_len(), r.max_read_len(), 1)
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
-            produced = counted(pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
-                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals))
+            produced = counted(trimmed(pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
+                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
                                         tail=tail, alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -297,7 +322,7 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         chunk_bytes: int = None, ref_chunk_bytes: int = None,
                         inflate: str = "host", tail: str = "host",
                         originals: bool = False, *, alignable_filter: str = None,
-                        read_filter=None) -> Tuple[List[ReadMatch], dict]:
+                        read_filter=None, adapter_trim=None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -340,41 +365,54 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     The counters gain ``reads_passed``, ``reads_trimmed``, ``bases_trimmed``, ``reads_too_short``,
     ``reads_too_many_n``, ``reads_low_quality`` and ``reads_mate_failed`` in front of the filter counts, the same on
     every route; ``pairs`` keeps counting every record.  ``ValueError`` for anything else.  Without it nothing more is
-    queued or allocated."""
+    queued or allocated.
+
+    ``adapter_trim``: None (the default), or an ``adapter_trim.AdapterTrim``: the records are cut to the insert on the
+    device between the FASTQ cut and the read filter (adapter_trim.py) — a pair whose mates read through a short
+    fragment into the adapters by the largest insert length at which they are each other's reverse complement, after
+    which ``fast_merge`` merges them; a read without such a mate by its adapter's sequence.  The record indices stay,
+    so names and ``m_original_reads`` are those of the records as the sequencer wrote them.  The counters gain
+    ``adapter_reads_cut``, ``adapter_bases_cut``, ``adapter_cut_by_overlap``, ``adapter_cut_by_sequence`` and
+    ``adapter_overlapping_pairs`` in front of the read filter's keys, the same on every route.  ``ValueError`` for
+    anything else.  Without it nothing more is queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
                              remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
-                             alignable_filter, read_filter)[:2]
+                             alignable_filter, read_filter, adapter_trim)[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
                          settings: Settings = None, chunk_bytes: int = None, ref_chunk_bytes: int = None,
                          inflate: str = "host", tail: str = "host", originals: bool = False,
                          remove_alignables: bool = False, *,
-                         alignable_filter: str = None, read_filter=None) -> Tuple[List[FusionResult], dict]:
+                         alignable_filter: str = None, read_filter=None,
+                         adapter_trim=None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
     the reference's stdout block, JSON file and HTML file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``,
     ``originals`` (what ``report_html`` shows under the supporting reads), ``remove_alignables`` (the reference's last
     filter as it is), ``alignable_filter`` (a last filter that works), ``read_filter`` (a quality filter ahead of the
-    scan): see ``scan_pair_end_files``.  ``tail``: "device" also clusters in bulk — the first fit of all
-    groups in one host call, the refined breaks of all matches in one ``gf_rp_adjust_device`` call (report_tail.py);
-    the same results, counters and report bytes."""
+    scan), ``adapter_trim`` (adapter trimming ahead of that): see ``scan_pair_end_files``.  ``tail``: "device" also
+    clusters in bulk — the first fit of all groups in one host call, the refined breaks of all matches in one
+    ``gf_rp_adjust_device`` call (report_tail.py); the same results, counters and report bytes."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
                                              settings.deletion_threshold, remove_alignables, chunk_bytes,
                                              ref_chunk_bytes, inflate, tail, originals, alignable_filter,
-                                             read_filter), settings, tail, device)
+                                             read_filter, adapter_trim), settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                         ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None,
-                        read_filter=None):
+                        read_filter=None, adapter_trim=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
+    from .adapter_trim import need_adapter_trim
     from .read_filter import need_read_filter
     from .report_tail import need_tail
     need_tail(tail)
     need_read_filter(read_filter)
+    if need_adapter_trim(adapter_trim) is not None and not adapter_trim.adapter_r1:
+        raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     _need_whole_contigs(alignable_filter, False, ref_chunk_bytes)
     if route not in ("device", "host"):
         raise ValueError("route must be 'device' or 'host', not %r" % (route,))
@@ -385,14 +423,16 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
         mapper = FusionMapper(ix)
         if chunk_bytes is not None:
             produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate, originals,
-                                      **({"read_filter": read_filter} if read_filter is not None else {}))
+                                      **({"read_filter": read_filter} if read_filter is not None else {}),
+                                      **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}))
         else:   # (both routes start from the records in HBM, where the read filter runs)
             b, text = FastqReader(read1_file).read_all_device(ix)
+            (b,), trimmed = trimmed_reads(ix, adapter_trim, b)
             (b,), counted = filtered_reads(ix, read_filter, b)
             if route == "device":
-                produced = counted(single_end_found(ix, mapper, b, text, originals))
+                produced = counted(trimmed(single_end_found(ix, mapper, b, text, originals)))
             else:
-                produced = counted(_single_end_host_found(mapper, b, text, originals))
+                produced = counted(trimmed(_single_end_host_found(mapper, b, text, originals)))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail,
                                         alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -403,7 +443,7 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           chunk_bytes: int = None, ref_chunk_bytes: int = None,
                           inflate: str = "host", tail: str = "host",
                           originals: bool = False, *, alignable_filter: str = None,
-                          read_filter=None) -> Tuple[List[ReadMatch], dict]:
+                          read_filter=None, adapter_trim=None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -419,21 +459,25 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     filters and the sort run, see ``scan_pair_end_files``.  ``originals``: every match carries its read's FASTQ
     record in ``m_original_reads``, on every route; see ``scan_pair_end_files``.  ``alignable_filter``: None or
     "genome", the whole-genome alignable filter on the device; see ``scan_pair_end_files``.  ``read_filter``: None or a
-    ``ReadFilter``, the quality filter ahead of the scan, on either route; see ``scan_pair_end_files``."""
+    ``ReadFilter``, the quality filter ahead of the scan, on either route; see ``scan_pair_end_files``.
+    ``adapter_trim``: None or an ``AdapterTrim`` with ``adapter_r1``, adapter trimming by sequence ahead of that, on
+    either route; ``ValueError`` without ``adapter_r1``; see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
-                               ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter)[:2]
+                               ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter,
+                               adapter_trim)[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
                            settings: Settings = None, route: str = "device", chunk_bytes: int = None,
                            ref_chunk_bytes: int = None, inflate: str = "host",
                            tail: str = "host", originals: bool = False, *,
-                           alignable_filter: str = None, read_filter=None) -> Tuple[List[FusionResult], dict]:
+                           alignable_filter: str = None, read_filter=None,
+                           adapter_trim=None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``: see
+    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``: see
     ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
                                                route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
-                                               alignable_filter, read_filter), settings, tail, device)
+                                               alignable_filter, read_filter, adapter_trim), settings, tail, device)

@@ -5,7 +5,8 @@ list happens on the device, chunk k+1 being read and crossing the link while chu
 
     byte source (a file, gunzipped as it is read; a text in memory)  --readinto, upload threads-->  pinned staging
     block  --H2D, copy stream-->  device text buffer (behind the carried-over tail of the previous chunk)  -->
-    gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_pp_filter_device, the read filter)  -->
+    gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_at_trim_device, the adapter trimming, and
+    gf_pp_filter_device, the read filter)  -->
     gf_scan_pairs_device (merge, map, reverse-complement
     retries, ordered compaction) or gf_se_scan_device  -->  gf_hn_names_device (the names of the hit records; on
     request gf_hn_records_device, their whole FASTQ records for the HTML report)  -->
@@ -163,27 +164,46 @@ def _filter_chunk(indexer: Indexer, read_filter, batches, m: int):
     return kept, totals
 
 
+def _trim_chunk(indexer: Indexer, adapter_trim, batches, m: int):
+    """The first ``m`` records of every side through the adapter trimming (adapter_trim.py), queued behind the cut and
+    ahead of ``_filter_chunk``: (the batches it leaves, of ``m`` records each; its totals, on the device)."""
+    from .adapter_trim import trim_adapters_device
+    *kept, totals = trim_adapters_device(indexer, adapter_trim,
+                                         *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches])
+    return kept, totals
+
+
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
-                scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None):
+                scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None):
     """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
     ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
     ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do).  ``read_filter``: a
     ``ReadFilter``, the records scanned go through the read filter between the cut — the full one, whatever ``lean``
     says — and the scan, and its totals are added to the totals of the chunk (of every index's, when ``scan_records``
-    gives a list) under ``read_filter.COUNTER_KEYS``."""
+    gives a list) under ``read_filter.COUNTER_KEYS``.  ``adapter_trim``: an ``AdapterTrim``, the same for the adapter
+    trimming, which runs between the cut and the read filter; its totals go under
+    ``adapter_trim.ADAPTER_COUNTER_KEYS``, in front of the read filter's."""
     from .fastq import fastq_cut_device
-    if read_filter is not None:
+    if read_filter is not None or adapter_trim is not None:
         lean = False
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
     lean = len(texts) > 1 if lean is None else lean
     batches = [fastq_cut_device(indexer, t, lean=lean) for t in texts]
     m, counts, cuts = _record_cuts(batches, texts, final, side_names)
-    if read_filter is not None and m > 0:
-        from .read_filter import totals_counters
-        kept, totals = _filter_chunk(indexer, read_filter, batches, m)
+    if (read_filter is not None or adapter_trim is not None) and m > 0:
+        kept, counted = batches, {}
+        if adapter_trim is not None:
+            from .adapter_trim import adapter_totals_counters
+            kept, trim_totals = _trim_chunk(indexer, adapter_trim, kept, m)
+        if read_filter is not None:
+            from .read_filter import totals_counters
+            kept, totals = _filter_chunk(indexer, read_filter, kept, m)
         out = scan_records(indexer, texts, kept, m, done, max_read_len, names)
-        counted = totals_counters(totals.cpu().tolist())
+        if adapter_trim is not None:
+            counted.update(adapter_totals_counters(trim_totals.cpu().tolist()))
+        if read_filter is not None:
+            counted.update(totals_counters(totals.cpu().tolist()))
         for per_index in (out if isinstance(out, list) else [out]):
             per_index[4].update(counted)
     else:
@@ -196,13 +216,16 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
 
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
-                        scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None):
+                        scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None,
+                        adapter_trim=None):
     """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
     for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
     of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``).  ``read_filter``: a ``ReadFilter``, handed
-    to ``_scan_chunk`` (only when set)."""
+    to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise."""
     import torch
     filtered = {} if read_filter is None else {"read_filter": read_filter}
+    if adapter_trim is not None:
+        filtered["adapter_trim"] = adapter_trim
     h = indexer._handle()
 
     def copy(ptr: int, dst: int, n: int, stream: int) -> None:
@@ -235,8 +258,8 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320, names: bool = True,
-                            originals: bool = False, *,
-                            read_filter=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            originals: bool = False, *, read_filter=None,
+                            adapter_trim=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
@@ -248,11 +271,15 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     record the (name, sequence, strand, quality) of R1 and of R2), gathered behind the scan before the chunk goes.
     ``read_filter``: a ``read_filter.ReadFilter``, every chunk's pairs go through the read filter between the cut —
     then the full one, the qualities at the bases' offsets — and the scan; the chunk's totals gain the filter's seven
-    counts (``read_filter.COUNTER_KEYS``).  None (the default): nothing more is queued."""
+    counts (``read_filter.COUNTER_KEYS``).  None (the default): nothing more is queued.  ``adapter_trim``: an
+    ``adapter_trim.AdapterTrim``, every chunk's pairs go through the adapter trimming between the cut — the full one
+    again — and the read filter or the scan; the chunk's totals gain its five counts
+    (``adapter_trim.ADAPTER_COUNTER_KEYS``).  None (the default): nothing more is queued."""
     scan_records = partial(_scan_records, originals=True) if originals else _scan_records
-    if read_filter is not None:
+    ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim)) if v is not None}
+    if ahead:
         return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
-                                   lean=False, read_filter=read_filter)
+                                   lean=False, **ahead)
     return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records)
 
 
@@ -268,18 +295,19 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
-                            names: bool = True, originals: bool = False, *,
-                            read_filter=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            names: bool = True, originals: bool = False, *, read_filter=None,
+                            adapter_trim=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
     trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
-    per hit record.  ``read_filter``: see ``scan_pair_source_stream``."""
+    per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``): see ``scan_pair_source_stream``."""
     if isinstance(source, np.ndarray):
         source = ArraySource(source)
     return _scan_source_stream(indexer, (source,), chunk_bytes, max_read_len, names,
                                partial(_scan_records, originals=True) if originals else _scan_records,
-                               **({} if read_filter is None else {"read_filter": read_filter}))
+                               **({} if read_filter is None else {"read_filter": read_filter}),
+                               **({} if adapter_trim is None else {"adapter_trim": adapter_trim}))
 
 
 def scan_pair_end_text(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
