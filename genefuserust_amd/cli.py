@@ -5,7 +5,8 @@ The options of the reference (src/argparse.rs) keep their letters and defaults â
 the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired or single-end), the HTML report and
 the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
 out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, the
-whole-genome alignable filter, and the adapter trimming and the quality filter of the reads ahead of the scan.
+whole-genome alignable filter, the adapter trimming and the quality filter of the reads ahead of the scan, and the
+QC report of the reads.
 """
 from __future__ import annotations
 
@@ -88,6 +89,12 @@ def parser() -> argparse.ArgumentParser:
                     "overlap, default 20")
     at.add_argument("--adapter-min-match", type=int, default=None, help="the fewest adapter bases looked for at a "
                     "read's end, default 10")
+    qc = p.add_argument_group("read QC (off by default)")
+    qc.add_argument("--qc-json", default=None, metavar="FILE", help="measure the reads on the device, before and behind "
+                    "the adapter trimming and the read filter, and write the QC report there: reads, bases, Q20/Q30, "
+                    "GC, per-cycle quality and base content, insert sizes; one file, also for a list of CSV files")
+    qc.add_argument("--qc-no-insert-size", action="store_true", help="leave the insert sizes of the pairs out of the "
+                    "QC report (needs --qc-json)")
     return p
 
 
@@ -119,6 +126,17 @@ def _adapter_trim(args):
         return None
     from .adapter_trim import AdapterTrim
     return AdapterTrim(**given)
+
+
+def _read_qc(args):
+    """The ``ReadQc`` the options ask for, None without ``--qc-json``; ``ValueError`` for ``--qc-no-insert-size``
+    without it."""
+    if not args.qc_json:
+        if args.qc_no_insert_size:
+            raise ValueError("--qc-no-insert-size needs --qc-json")
+        return None
+    from .read_qc import ReadQc
+    return ReadQc(insert_size=not args.qc_no_insert_size)
 
 
 def _missing(args) -> Optional[str]:
@@ -154,6 +172,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         adapter_trim = _adapter_trim(args)
         if adapter_trim is not None:
             common["adapter_trim"] = adapter_trim
+        qc = _read_qc(args)
+        if qc is not None:
+            common["qc"] = qc
         if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
@@ -168,6 +189,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         print("ERROR: %s" % e, file=sys.stderr)
         return 1
     per_csv: List = [r for _, r, _ in out] if isinstance(out, list) else [out[0]]
+    if qc is not None:   # (one file: every CSV of a list saw the same reads, and counts the same trimming and filter)
+        from .read_qc import report_json
+        counters = (out[0][2] if out else None) if isinstance(out, list) else out[1]
+        with open(args.qc_json, "w") as f:
+            f.write(report_json(qc.result(), counters))
     for results in per_csv:
         sys.stdout.write(report_text(results))
     print("# genefuse v%s, time used: %s seconds\n" % (__version__, time.monotonic() - started))

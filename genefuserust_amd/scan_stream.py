@@ -173,8 +173,15 @@ def _trim_chunk(indexer: Indexer, adapter_trim, batches, m: int):
     return kept, totals
 
 
+def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
+    """The first ``m`` records of every side added to the tables of ``qc`` (read_qc.py) for ``stage``, queued behind
+    what made them.  The records behind them are carried to the next chunk and measured there, once."""
+    qc.measure(indexer, stage, *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches])
+
+
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
-                scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None):
+                scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None,
+                qc=None):
     """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
     ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
     ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do).  ``read_filter``: a
@@ -182,15 +189,19 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     says — and the scan, and its totals are added to the totals of the chunk (of every index's, when ``scan_records``
     gives a list) under ``read_filter.COUNTER_KEYS``.  ``adapter_trim``: an ``AdapterTrim``, the same for the adapter
     trimming, which runs between the cut and the read filter; its totals go under
-    ``adapter_trim.ADAPTER_COUNTER_KEYS``, in front of the read filter's."""
+    ``adapter_trim.ADAPTER_COUNTER_KEYS``, in front of the read filter's.  ``qc``: a ``ReadQc``, the first ``m``
+    records of every side — the rest are carried into the next chunk and measured there — are added to its tables
+    between the cut, the full one again, and the trimming, and behind the read filter when either of the two runs."""
     from .fastq import fastq_cut_device
-    if read_filter is not None or adapter_trim is not None:
+    if read_filter is not None or adapter_trim is not None or qc is not None:
         lean = False
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
     lean = len(texts) > 1 if lean is None else lean
     batches = [fastq_cut_device(indexer, t, lean=lean) for t in texts]
     m, counts, cuts = _record_cuts(batches, texts, final, side_names)
+    if qc is not None and m > 0:
+        _measure_chunk(indexer, qc, "before", batches, m)
     if (read_filter is not None or adapter_trim is not None) and m > 0:
         kept, counted = batches, {}
         if adapter_trim is not None:
@@ -199,6 +210,8 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
         if read_filter is not None:
             from .read_filter import totals_counters
             kept, totals = _filter_chunk(indexer, read_filter, kept, m)
+        if qc is not None:
+            _measure_chunk(indexer, qc, "after", kept, m)
         out = scan_records(indexer, texts, kept, m, done, max_read_len, names)
         if adapter_trim is not None:
             counted.update(adapter_totals_counters(trim_totals.cpu().tolist()))
@@ -217,15 +230,17 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
                         scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None,
-                        adapter_trim=None):
+                        adapter_trim=None, qc=None):
     """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
     for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
     of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``).  ``read_filter``: a ``ReadFilter``, handed
-    to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise."""
+    to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise; ``qc``: a ``ReadQc``, likewise."""
     import torch
     filtered = {} if read_filter is None else {"read_filter": read_filter}
     if adapter_trim is not None:
         filtered["adapter_trim"] = adapter_trim
+    if qc is not None:
+        filtered["qc"] = qc
     h = indexer._handle()
 
     def copy(ptr: int, dst: int, n: int, stream: int) -> None:
@@ -258,8 +273,8 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320, names: bool = True,
-                            originals: bool = False, *, read_filter=None,
-                            adapter_trim=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            originals: bool = False, *, read_filter=None, adapter_trim=None,
+                            qc=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
@@ -274,9 +289,14 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     counts (``read_filter.COUNTER_KEYS``).  None (the default): nothing more is queued.  ``adapter_trim``: an
     ``adapter_trim.AdapterTrim``, every chunk's pairs go through the adapter trimming between the cut — the full one
     again — and the read filter or the scan; the chunk's totals gain its five counts
-    (``adapter_trim.ADAPTER_COUNTER_KEYS``).  None (the default): nothing more is queued."""
+    (``adapter_trim.ADAPTER_COUNTER_KEYS``).  None (the default): nothing more is queued.  ``qc``: a
+    ``read_qc.ReadQc``, every chunk's pairs are measured between the cut — the full one again — and the trimming, and
+    behind the read filter when either of the two runs; what is yielded stays as it is.  None (the default): nothing
+    more is queued."""
+    from .read_qc import need_read_qc
     scan_records = partial(_scan_records, originals=True) if originals else _scan_records
-    ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim)) if v is not None}
+    ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim),
+                               ("qc", need_read_qc(qc))) if v is not None}
     if ahead:
         return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
                                    lean=False, **ahead)
@@ -295,19 +315,23 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
-                            names: bool = True, originals: bool = False, *, read_filter=None,
-                            adapter_trim=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            names: bool = True, originals: bool = False, *, read_filter=None, adapter_trim=None,
+                            qc=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
     trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
-    per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``): see ``scan_pair_source_stream``."""
+    per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``), ``qc``: see
+    ``scan_pair_source_stream``."""
+    from .read_qc import need_read_qc
+    need_read_qc(qc)
     if isinstance(source, np.ndarray):
         source = ArraySource(source)
     return _scan_source_stream(indexer, (source,), chunk_bytes, max_read_len, names,
                                partial(_scan_records, originals=True) if originals else _scan_records,
                                **({} if read_filter is None else {"read_filter": read_filter}),
-                               **({} if adapter_trim is None else {"adapter_trim": adapter_trim}))
+                               **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
+                               **({} if qc is None else {"qc": qc}))
 
 
 def scan_pair_end_text(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
