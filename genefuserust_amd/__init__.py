@@ -18,5 +18,6 @@ from .multi_csv_scan import (PreparedPairs, prepare_pairs_device, read_csv_list,
 from .read_filter import ReadFilter, filter_reads_device  # noqa: F401
 from .adapter_trim import AdapterTrim, trim_adapters_device  # noqa: F401
 from .read_qc import ReadQc, QcResult  # noqa: F401
+from .dedup import Dedup, DedupResult  # noqa: F401
 
 __version__ = "0.1.0"

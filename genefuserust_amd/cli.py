@@ -5,8 +5,8 @@ The options of the reference (src/argparse.rs) keep their letters and defaults â
 the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired or single-end), the HTML report and
 the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
 out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, the
-whole-genome alignable filter, the adapter trimming and the quality filter of the reads ahead of the scan, and the
-QC report of the reads.
+whole-genome alignable filter, the adapter trimming, the quality filter and the duplicate removal of the reads ahead of
+the scan, and the QC report of the reads.
 """
 from __future__ import annotations
 
@@ -95,6 +95,13 @@ def parser() -> argparse.ArgumentParser:
                     "GC, per-cycle quality and base content, insert sizes; one file, also for a list of CSV files")
     qc.add_argument("--qc-no-insert-size", action="store_true", help="leave the insert sizes of the pairs out of the "
                     "QC report (needs --qc-json)")
+    dd = p.add_argument_group("duplicate removal (off by default; any of its options switches it on)")
+    dd.add_argument("--dedup", action="store_true", help="find duplicate pairs (reads) on the device behind the read "
+                    "filter, by their bases with the case folded, and scan only the first of each; with --qc-json the "
+                    "report gains the duplication rate")
+    dd.add_argument("--dedup-count-only", action="store_true", help="count the duplicates, remove none")
+    dd.add_argument("--dedup-max-slots", type=int, default=None, metavar="N", help="the largest hash table, a power "
+                    "of two of slots of 20 bytes, default 2^31; a table grows to twice the records offered")
     return p
 
 
@@ -139,6 +146,17 @@ def _read_qc(args):
     return ReadQc(insert_size=not args.qc_no_insert_size)
 
 
+def _dedup(args):
+    """The ``Dedup`` the options ask for, None when none of them is given; ``ValueError`` for a value out of range."""
+    if not (args.dedup or args.dedup_count_only or args.dedup_max_slots is not None):
+        return None
+    from .dedup import Dedup
+    sizes = {}
+    if args.dedup_max_slots is not None:   # (a small limit takes the first size down with it)
+        sizes = dict(max_slots=args.dedup_max_slots, slots=min(Dedup().slots, max(args.dedup_max_slots, 1)))
+    return Dedup(remove=not args.dedup_count_only, **sizes)
+
+
 def _missing(args) -> Optional[str]:
     """genefuse.rs:75-84: the first input file that is not there."""
     for f in (args.ref, args.read1, args.read2, args.fusion):
@@ -175,6 +193,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         qc = _read_qc(args)
         if qc is not None:
             common["qc"] = qc
+        dedup = _dedup(args)
+        if dedup is not None:
+            common["dedup"] = dedup
         if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
@@ -193,7 +214,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from .read_qc import report_json
         counters = (out[0][2] if out else None) if isinstance(out, list) else out[1]
         with open(args.qc_json, "w") as f:
-            f.write(report_json(qc.result(), counters))
+            f.write(report_json(qc.result(), counters, **({} if dedup is None else {"duplication": dedup.result()})))
     for results in per_csv:
         sys.stdout.write(report_text(results))
     print("# genefuse v%s, time used: %s seconds\n" % (__version__, time.monotonic() - started))

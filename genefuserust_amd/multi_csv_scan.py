@@ -158,7 +158,7 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
 def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host",
-                      originals: bool = False, *, read_filter=None, adapter_trim=None, qc=None):
+                      originals: bool = False, *, read_filter=None, adapter_trim=None, qc=None, dedup=None):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
@@ -172,9 +172,11 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     (``scan_stream._scan_chunk``); every index reports the same filter totals, in front of its filter counts.
     ``adapter_trim``: an ``AdapterTrim``, the same for the adapter trimming ahead of the read filter; its totals stand in
     front of the read filter's.  ``qc``: a ``ReadQc``, every chunk's records are measured once, before and behind the
-    two (``scan_stream._scan_chunk``), never per index."""
+    two (``scan_stream._scan_chunk``), never per index.  ``dedup``: a ``Dedup``, every chunk's records are
+    deduplicated once, behind the read filter; every index reports the same four totals behind the read filter's."""
     from . import scan_pack, scan_stream
     from .adapter_trim import ADAPTER_COUNTER_KEYS
+    from .dedup import DEDUP_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
     from .fusion_mapper import FusionMapper
     from .read_pair import finish_pair_hits
@@ -185,7 +187,8 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     mappers = [FusionMapper(ix) for ix in indexers]
     found = [[] for _ in indexers]
     sums = [{count_key: 0, "merged_pairs": 0, "retried_reads": 0} for _ in indexers]
-    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS)
+    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS) \
+        + (() if dedup is None else DEDUP_COUNTER_KEYS)
     for t in sums:
         t.update(dict.fromkeys(extra, 0))
     chunks = 0
@@ -231,7 +234,8 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
                                                                         {"read_filter": read_filter}),
                                                          **({} if adapter_trim is None else
                                                             {"adapter_trim": adapter_trim}),
-                                                         **({} if qc is None else {"qc": qc})):
+                                                         **({} if qc is None else {"qc": qc}),
+                                                         **({} if dedup is None else {"dedup": dedup})):
             for k, (rec, hb, hq, names, tot, *orig) in enumerate(per_index):
                 found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names, *orig)
                 for key in sums[k]:
@@ -250,7 +254,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
                           hits_cap: int = None, inflate: str = "host", tail: str = "host", originals: bool = False,
                           html_file: str = "", *, read_filter=None, adapter_trim=None,
-                          qc=None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          qc=None, dedup=None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -287,8 +291,13 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     needs ``adapter_r1``.
 
     ``qc``: None or a ``read_qc.ReadQc``, the reads measured before and behind the two (``scan.scan_pair_end_files``):
-    once — over the resident records before the loop over the CSVs, or once per chunk — never per index."""
+    once — over the resident records before the loop over the CSVs, or once per chunk — never per index.
+
+    ``dedup``: None or a ``dedup.Dedup``, duplicate records removed behind the read filter
+    (``scan.scan_pair_end_files``): once as well — a list of CSVs is deduplicated once — and every CSV reports the same
+    four totals."""
     from .adapter_trim import need_adapter_trim
+    from .dedup import need_dedup
     from .fastq import FastqReader, FastqReaderPair
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
@@ -296,11 +305,12 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     need_tail(tail)
     need_read_filter(read_filter)
     need_read_qc(qc)
+    need_dedup(dedup)
     if need_adapter_trim(adapter_trim) is not None and not read2_file and not adapter_trim.adapter_r1:
         raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     from .fusion_mapper import FusionMapper
     from .indexer import Fusion
-    from .scan import (GeneSlices, _route_inflate, filtered_reads, finish_matches, measured_reads, open_index,
+    from .scan import (GeneSlices, _route_inflate, deduplicated_reads, filtered_reads, finish_matches, measured_reads, open_index,
                        pairs_found, read_contigs, report_matches, single_end_found, trimmed_reads)
     settings = settings or Settings()
     fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
@@ -327,7 +337,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
             produced = (_stream_multi_csv([ix for ix, _ in opened], files, chunk_bytes, hits_cap, fq_inflate, originals,
                                           **({} if read_filter is None else {"read_filter": read_filter}),
                                           **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
-                                          **({} if qc is None else {"qc": qc}))
+                                          **({} if qc is None else {"qc": qc}),
+                                          **({} if dedup is None else {"dedup": dedup}))
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
@@ -336,7 +347,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
         for k, (_, results, _) in enumerate(out):
             write(k, results)
         return out
-    reads = prepared = counted = trimmed = None
+    reads = prepared = counted = trimmed = deduplicated = None
     for k, csv in enumerate(csvs):
         with open_index(refs[k], csv, device) as (ix, fusions):
             if reads is None:   # (the first index names the device the records go to)
@@ -345,7 +356,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                     measured_reads(ix, qc, "before", l, r)
                     (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
                     (l, r), counted = filtered_reads(ix, read_filter, l, r)
-                    if adapter_trim is not None or read_filter is not None:
+                    (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r)
+                    if adapter_trim is not None or read_filter is not None or dedup is not None:
                         measured_reads(ix, qc, "after", l, r)
                     reads = (l, ltext), (r, rtext)
                     prepared = prepare_pairs_device(ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets,
@@ -355,7 +367,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                     measured_reads(ix, qc, "before", b)
                     (b,), trimmed = trimmed_reads(ix, adapter_trim, b)
                     (b,), counted = filtered_reads(ix, read_filter, b)
-                    if adapter_trim is not None or read_filter is not None:
+                    (b,), deduplicated = deduplicated_reads(ix, dedup, b)
+                    if adapter_trim is not None or read_filter is not None or dedup is not None:
                         measured_reads(ix, qc, "after", b)
                     reads = b, text
             mapper = FusionMapper(ix)
@@ -364,7 +377,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                        lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps), originals)
             else:
                 produced = single_end_found(ix, mapper, *reads, originals)
-            produced = counted(trimmed(produced))
+            produced = deduplicated(counted(trimmed(produced)))
             kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:],
                                             tail=tail)
             results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)
@@ -377,7 +390,7 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
                 chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
                 originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False, *,
-                alignable_filter: str = None, read_filter=None, adapter_trim=None, qc=None):
+                alignable_filter: str = None, read_filter=None, adapter_trim=None, qc=None, dedup=None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -395,9 +408,11 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     mode (``scan.scan_pair_end_files``); it is handed on only when set.  ``adapter_trim``: None or an
     ``adapter_trim.AdapterTrim``, adapter trimming ahead of the read filter, in every mode, handed on only when set.
     ``qc``: None or a ``read_qc.ReadQc``, the reads measured before and behind the two, in every mode, handed on only
-    when set; for a list of CSVs the reads are measured once."""
+    when set; for a list of CSVs the reads are measured once.  ``dedup``: None or a ``dedup.Dedup``, duplicate records
+    removed behind the read filter, in every mode, handed on only when set; a list of CSVs is deduplicated once."""
     from . import scan
     from .adapter_trim import need_adapter_trim
+    from .dedup import need_dedup
     from .alignable import need_filter
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
@@ -406,6 +421,8 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         filtered["adapter_trim"] = adapter_trim
     if need_read_qc(qc) is not None:
         filtered["qc"] = qc
+    if need_dedup(dedup) is not None:
+        filtered["dedup"] = dedup
     if need_filter(alignable_filter, remove_alignables) and _rust_stem_ext(fusion_file)[2] != "csv":
         raise ValueError("alignable_filter: only the scans of one CSV have this filter")
     if remove_alignables and not (_rust_stem_ext(fusion_file)[2] == "csv" and read2_file):

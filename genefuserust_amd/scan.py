@@ -127,6 +127,23 @@ def filtered_reads(ix: Indexer, read_filter, *batches):
     return tuple(kept), counted
 
 
+def deduplicated_reads(ix: Indexer, dedup, *batches):
+    """The ``FastqBatch``es (a file's records, or a pair's) through the duplicate removal on the index's device
+    (dedup.py), behind ``filtered_reads`` and in front of the scan: (the batches it leaves, ``counted(produced)``).
+    ``counted`` adds the four ``dedup_*`` totals to the end of a producer's counters in front of the filter counts — so it
+    is applied behind ``filtered_reads``' — and ``dedup`` None gives the batches as they are, nothing queued, and a
+    ``counted`` that changes nothing."""
+    if dedup is None:
+        return batches, lambda produced: produced
+    from .dedup import dedup_totals_counters
+    kept, totals = dedup.apply(ix, *batches)
+
+    def counted(produced):
+        found, before, after = produced
+        return found, {**before, **dedup_totals_counters(totals.cpu().tolist(), dedup.remove)}, after
+    return tuple(kept), counted
+
+
 def trimmed_reads(ix: Indexer, adapter_trim, *batches):
     """The ``FastqBatch``es (a file's records, or a pair's) through the adapter trimming on the index's device
     (adapter_trim.py), ahead of ``filtered_reads``: (the batches it leaves, ``counted(produced)``).  ``counted`` adds the
@@ -237,7 +254,7 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
 
 def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
                    originals: bool = False, *, read_filter=None,
-                   adapter_trim=None, qc=None) -> Tuple[List[ReadMatch], dict, dict]:
+                   adapter_trim=None, qc=None, dedup=None) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
     order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
     ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``).
@@ -245,26 +262,31 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     (``scan_stream._scan_chunk``) and its totals, summed over the chunks, end the counters in front of the filter
     counts.  ``adapter_trim``: an ``AdapterTrim``, every chunk's records go through the adapter trimming ahead of that,
     and its five totals stand in front of the read filter's.  ``qc``: a ``ReadQc``, every chunk's records are measured
-    before and behind the two (``scan_stream._scan_chunk``); the counters stay as they are."""
+    before and behind the two (``scan_stream._scan_chunk``); the counters stay as they are.  ``dedup``: a ``Dedup``,
+    every chunk's records go through the duplicate removal behind the read filter, and its four totals stand behind
+    the read filter's."""
     from .adapter_trim import ADAPTER_COUNTER_KEYS
+    from .dedup import DEDUP_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
     from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
     count_key = "pairs" if len(files) == 2 else "reads"
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
     found: List[ReadMatch] = []
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
-    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS)
+    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS) \
+        + (() if dedup is None else DEDUP_COUNTER_KEYS)
     sums.update(dict.fromkeys(extra, 0))
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        # (originals=False, read_filter=None, adapter_trim=None and qc=None are not passed on: the stream is then
-        #  called as it always was)
+        # (originals=False, read_filter=None, adapter_trim=None, qc=None and dedup=None are not passed on: the stream is
+        #  then called as it always was)
         for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
                                                      **({"originals": True} if originals else {}),
                                                      **({"read_filter": read_filter} if read_filter is not None else {}),
                                                      **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
-                                                     **({"qc": qc} if qc is not None else {})):
+                                                     **({"qc": qc} if qc is not None else {}),
+                                                     **({"dedup": dedup} if dedup is not None else {})):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
@@ -293,9 +315,10 @@ def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) ->
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
                       chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
-                      alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None):
+                      alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None, dedup=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
     from .adapter_trim import need_adapter_trim
+    from .dedup import need_dedup
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
     from .report_tail import need_tail
@@ -303,6 +326,7 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
     need_read_filter(read_filter)
     need_adapter_trim(adapter_trim)
     need_read_qc(qc)
+    need_dedup(dedup)
     _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
@@ -314,19 +338,21 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
             produced = streamed_found(ix, mapper, (read1_file, read2_file), chunk_bytes, fq_inflate, originals,
                                       **({"read_filter": read_filter} if read_filter is not None else {}),
                                       **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
-                                      **({"qc": qc} if qc is not None else {}))
+                                      **({"qc": qc} if qc is not None else {}),
+                                      **({"dedup": dedup} if dedup is not None else {}))
         else:
             (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
             measured_reads(ix, qc, "before", l, r)
             (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
             (l, r), counted = filtered_reads(ix, read_filter, l, r)
-            if adapter_trim is not None or read_filter is not None:
+            (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r)
+            if adapter_trim is not None or read_filter is not None or dedup is not None:
                 measured_reads(ix, qc, "after", l, r)
             reads = (l, ltext), (r, rtext)
             max_len = max(l.max_read_len(), r.max_read_len(), 1)
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
-            produced = counted(trimmed(pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
-                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)))
+            produced = deduplicated(counted(trimmed(pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
+                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals))))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
                                         tail=tail, alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -337,7 +363,8 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         chunk_bytes: int = None, ref_chunk_bytes: int = None,
                         inflate: str = "host", tail: str = "host",
                         originals: bool = False, *, alignable_filter: str = None,
-                        read_filter=None, adapter_trim=None, qc=None) -> Tuple[List[ReadMatch], dict]:
+                        read_filter=None, adapter_trim=None, qc=None,
+                        dedup=None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -395,10 +422,20 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     the FASTQ cut and the adapter trimming — per-cycle quality and base content, read lengths, and the pairs' insert
     sizes — and again behind the read filter when either of the two runs; ``qc.result()`` has the tables and
     ``read_qc.report_json`` the document.  Matches and counters are those of the scan without it, on every route.
-    ``ValueError`` for anything else.  Without it nothing more is queued or allocated."""
+    ``ValueError`` for anything else.  Without it nothing more is queued or allocated.
+
+    ``dedup``: None (the default), or a ``dedup.Dedup``: duplicate pairs are found on the device (dedup.py) behind the
+    read filter — so by the bases of the trimmed records — and in front of the scan: of the pairs with the same bases,
+    case folded, the first in file order is scanned and every other one as two empty reads (``Dedup(remove=False)`` only
+    counts them).  The record indices stay, so a match is named after the first copy.  ``qc``'s "after" stage is then
+    measured behind this step.  The counters gain ``dedup_checked``, ``dedup_unique``, ``dedup_duplicates`` and
+    ``dedup_bases_removed`` behind the read filter's keys, the same on every route; ``dedup.result()`` has the rate and
+    the histogram.  One ``Dedup`` handed to two scans removes the duplicates across them.  ``ValueError`` for anything
+    else.  Without it nothing more is queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
                              remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
-                             alignable_filter, read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}))[:2]
+                             alignable_filter, read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
+                             **({"dedup": dedup} if dedup is not None else {}))[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
@@ -406,36 +443,39 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                          inflate: str = "host", tail: str = "host", originals: bool = False,
                          remove_alignables: bool = False, *,
                          alignable_filter: str = None, read_filter=None,
-                         adapter_trim=None, qc=None) -> Tuple[List[FusionResult], dict]:
+                         adapter_trim=None, qc=None, dedup=None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
     the reference's stdout block, JSON file and HTML file.  ``chunk_bytes``, ``ref_chunk_bytes``, ``inflate``,
     ``originals`` (what ``report_html`` shows under the supporting reads), ``remove_alignables`` (the reference's last
     filter as it is), ``alignable_filter`` (a last filter that works), ``read_filter`` (a quality filter ahead of the
-    scan), ``adapter_trim`` (adapter trimming ahead of that), ``qc`` (the reads measured before and behind the two): see
-    ``scan_pair_end_files``.  ``tail``: "device" also
+    scan), ``adapter_trim`` (adapter trimming ahead of that), ``qc`` (the reads measured before and behind the two),
+    ``dedup`` (duplicate pairs removed behind the read filter): see ``scan_pair_end_files``.  ``tail``: "device" also
     clusters in bulk — the first fit of all groups in one host call, the refined breaks of all matches in one
     ``gf_rp_adjust_device`` call (report_tail.py); the same results, counters and report bytes."""
     settings = settings or Settings()
     return report_matches(*_pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device,
                                              settings.deletion_threshold, remove_alignables, chunk_bytes,
                                              ref_chunk_bytes, inflate, tail, originals, alignable_filter,
-                                             read_filter, adapter_trim, **({"qc": qc} if qc is not None else {})),
+                                             read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
+                                             **({"dedup": dedup} if dedup is not None else {})),
                           settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                         ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None,
-                        read_filter=None, adapter_trim=None, *, qc=None):
+                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     from .adapter_trim import need_adapter_trim
+    from .dedup import need_dedup
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
     from .report_tail import need_tail
     need_tail(tail)
     need_read_filter(read_filter)
     need_read_qc(qc)
+    need_dedup(dedup)
     if need_adapter_trim(adapter_trim) is not None and not adapter_trim.adapter_r1:
         raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     _need_whole_contigs(alignable_filter, False, ref_chunk_bytes)
@@ -450,18 +490,20 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
             produced = streamed_found(ix, mapper, (read1_file,), chunk_bytes, fq_inflate, originals,
                                       **({"read_filter": read_filter} if read_filter is not None else {}),
                                       **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
-                                      **({"qc": qc} if qc is not None else {}))
+                                      **({"qc": qc} if qc is not None else {}),
+                                      **({"dedup": dedup} if dedup is not None else {}))
         else:   # (both routes start from the records in HBM, where the read filter runs)
             b, text = FastqReader(read1_file).read_all_device(ix)
             measured_reads(ix, qc, "before", b)
             (b,), trimmed = trimmed_reads(ix, adapter_trim, b)
             (b,), counted = filtered_reads(ix, read_filter, b)
-            if adapter_trim is not None or read_filter is not None:
+            (b,), deduplicated = deduplicated_reads(ix, dedup, b)
+            if adapter_trim is not None or read_filter is not None or dedup is not None:
                 measured_reads(ix, qc, "after", b)
             if route == "device":
-                produced = counted(trimmed(single_end_found(ix, mapper, b, text, originals)))
+                produced = deduplicated(counted(trimmed(single_end_found(ix, mapper, b, text, originals))))
             else:
-                produced = counted(trimmed(_single_end_host_found(mapper, b, text, originals)))
+                produced = deduplicated(counted(trimmed(_single_end_host_found(mapper, b, text, originals))))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail,
                                         alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -472,7 +514,8 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           chunk_bytes: int = None, ref_chunk_bytes: int = None,
                           inflate: str = "host", tail: str = "host",
                           originals: bool = False, *, alignable_filter: str = None,
-                          read_filter=None, adapter_trim=None, qc=None) -> Tuple[List[ReadMatch], dict]:
+                          read_filter=None, adapter_trim=None, qc=None,
+                        dedup=None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -492,10 +535,12 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     ``adapter_trim``: None or an ``AdapterTrim`` with ``adapter_r1``, adapter trimming by sequence ahead of that, on
     either route; ``ValueError`` without ``adapter_r1``; see ``scan_pair_end_files``.  ``qc``: None or a ``ReadQc``,
     the reads measured before and behind the two, on either route (no insert sizes: there are no pairs); see
-    ``scan_pair_end_files``."""
+    ``scan_pair_end_files``.  ``dedup``: None or a ``Dedup``, duplicate reads removed behind the read filter, on either
+    route; see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                                ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter,
-                               adapter_trim, **({"qc": qc} if qc is not None else {}))[:2]
+                               adapter_trim, **({"qc": qc} if qc is not None else {}),
+                               **({"dedup": dedup} if dedup is not None else {}))[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
@@ -503,13 +548,14 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                            ref_chunk_bytes: int = None, inflate: str = "host",
                            tail: str = "host", originals: bool = False, *,
                            alignable_filter: str = None, read_filter=None,
-                           adapter_trim=None, qc=None) -> Tuple[List[FusionResult], dict]:
+                           adapter_trim=None, qc=None, dedup=None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``, ``qc``: see
+    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``, ``qc``, ``dedup``: see
     ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
     return report_matches(*_single_end_matches(ref_file, fusion_csv, read1_file, device, settings.deletion_threshold,
                                                route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
                                                alignable_filter, read_filter, adapter_trim,
-                                               **({"qc": qc} if qc is not None else {})), settings, tail, device)
+                                               **({"qc": qc} if qc is not None else {}),
+                                               **({"dedup": dedup} if dedup is not None else {})), settings, tail, device)

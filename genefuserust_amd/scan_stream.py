@@ -6,7 +6,7 @@ list happens on the device, chunk k+1 being read and crossing the link while chu
     byte source (a file, gunzipped as it is read; a text in memory)  --readinto, upload threads-->  pinned staging
     block  --H2D, copy stream-->  device text buffer (behind the carried-over tail of the previous chunk)  -->
     gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_at_trim_device, the adapter trimming, and
-    gf_pp_filter_device, the read filter)  -->
+    gf_pp_filter_device, the read filter, and the gf_dd_* calls, the duplicate removal)  -->
     gf_scan_pairs_device (merge, map, reverse-complement
     retries, ordered compaction) or gf_se_scan_device  -->  gf_hn_names_device (the names of the hit records; on
     request gf_hn_records_device, their whole FASTQ records for the HTML report)  -->
@@ -59,7 +59,8 @@ def _chunk_reads(batches, m: int, max_read_len: Optional[int]):
     """(offsets, base bytes, max_read_len) of the first ``m`` records of every side.  ``max_read_len`` None: the longest
     read of the chunk, as the whole-file scans take the longest of the file."""
     offs = [b.offsets[:m + 1] for b in batches]
-    nb = [int(o[-1].item()) for o in offs]
+    # (at least one byte: a chunk whose records the filter or the duplicate removal all emptied still has an address)
+    nb = [max(int(o[-1].item()), 1) for o in offs]
     mrl = max_read_len
     if mrl is None:
         mrl = max([int((o[1:] - o[:-1]).max().item()) for o in offs] + [1])
@@ -173,6 +174,14 @@ def _trim_chunk(indexer: Indexer, adapter_trim, batches, m: int):
     return kept, totals
 
 
+def _dedup_chunk(indexer: Indexer, dedup, batches, m: int):
+    """The first ``m`` records of every side through the duplicate removal (dedup.py), queued behind ``_filter_chunk``:
+    (the batches it leaves, of ``m`` records each; its totals, on the device).  Only these ``m`` are offered to the
+    table: the records behind them are carried to the next chunk and offered there, once, so that the indices the table
+    counts are the files'."""
+    return dedup.apply(indexer, *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches])
+
+
 def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
     """The first ``m`` records of every side added to the tables of ``qc`` (read_qc.py) for ``stage``, queued behind
     what made them.  The records behind them are carried to the next chunk and measured there, once."""
@@ -181,7 +190,7 @@ def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
 
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
                 scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None,
-                qc=None):
+                qc=None, dedup=None):
     """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
     ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
     ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do).  ``read_filter``: a
@@ -191,9 +200,11 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     trimming, which runs between the cut and the read filter; its totals go under
     ``adapter_trim.ADAPTER_COUNTER_KEYS``, in front of the read filter's.  ``qc``: a ``ReadQc``, the first ``m``
     records of every side — the rest are carried into the next chunk and measured there — are added to its tables
-    between the cut, the full one again, and the trimming, and behind the read filter when either of the two runs."""
+    between the cut, the full one again, and the trimming, and behind the last of the steps when any of them runs.
+    ``dedup``: a ``Dedup``, the same for the duplicate removal, which runs last, behind the read filter — the full cut
+    again; its totals go under ``dedup.DEDUP_COUNTER_KEYS``, behind the read filter's."""
     from .fastq import fastq_cut_device
-    if read_filter is not None or adapter_trim is not None or qc is not None:
+    if read_filter is not None or adapter_trim is not None or qc is not None or dedup is not None:
         lean = False
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
@@ -202,7 +213,7 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     m, counts, cuts = _record_cuts(batches, texts, final, side_names)
     if qc is not None and m > 0:
         _measure_chunk(indexer, qc, "before", batches, m)
-    if (read_filter is not None or adapter_trim is not None) and m > 0:
+    if (read_filter is not None or adapter_trim is not None or dedup is not None) and m > 0:
         kept, counted = batches, {}
         if adapter_trim is not None:
             from .adapter_trim import adapter_totals_counters
@@ -210,6 +221,9 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
         if read_filter is not None:
             from .read_filter import totals_counters
             kept, totals = _filter_chunk(indexer, read_filter, kept, m)
+        if dedup is not None:
+            from .dedup import dedup_totals_counters
+            kept, dedup_totals = _dedup_chunk(indexer, dedup, kept, m)
         if qc is not None:
             _measure_chunk(indexer, qc, "after", kept, m)
         out = scan_records(indexer, texts, kept, m, done, max_read_len, names)
@@ -217,6 +231,8 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
             counted.update(adapter_totals_counters(trim_totals.cpu().tolist()))
         if read_filter is not None:
             counted.update(totals_counters(totals.cpu().tolist()))
+        if dedup is not None:
+            counted.update(dedup_totals_counters(dedup_totals.cpu().tolist(), dedup.remove))
         for per_index in (out if isinstance(out, list) else [out]):
             per_index[4].update(counted)
     else:
@@ -230,17 +246,20 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
                         scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None,
-                        adapter_trim=None, qc=None):
+                        adapter_trim=None, qc=None, dedup=None):
     """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
     for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
     of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``).  ``read_filter``: a ``ReadFilter``, handed
-    to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise; ``qc``: a ``ReadQc``, likewise."""
+    to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise; ``qc``: a ``ReadQc``, likewise;
+    ``dedup``: a ``Dedup``, likewise."""
     import torch
     filtered = {} if read_filter is None else {"read_filter": read_filter}
     if adapter_trim is not None:
         filtered["adapter_trim"] = adapter_trim
     if qc is not None:
         filtered["qc"] = qc
+    if dedup is not None:
+        filtered["dedup"] = dedup
     h = indexer._handle()
 
     def copy(ptr: int, dst: int, n: int, stream: int) -> None:
@@ -274,7 +293,7 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320, names: bool = True,
                             originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
@@ -292,11 +311,14 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     (``adapter_trim.ADAPTER_COUNTER_KEYS``).  None (the default): nothing more is queued.  ``qc``: a
     ``read_qc.ReadQc``, every chunk's pairs are measured between the cut — the full one again — and the trimming, and
     behind the read filter when either of the two runs; what is yielded stays as it is.  None (the default): nothing
-    more is queued."""
+    more is queued.  ``dedup``: a ``dedup.Dedup``, every chunk's pairs go through the duplicate removal behind the read
+    filter — the full cut again — and ``qc``'s "after" stage moves behind it; the chunk's totals gain its four counts
+    (``dedup.DEDUP_COUNTER_KEYS``).  None (the default): nothing more is queued.  ``ValueError`` for anything else."""
+    from .dedup import need_dedup
     from .read_qc import need_read_qc
     scan_records = partial(_scan_records, originals=True) if originals else _scan_records
     ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim),
-                               ("qc", need_read_qc(qc))) if v is not None}
+                               ("qc", need_read_qc(qc)), ("dedup", need_dedup(dedup))) if v is not None}
     if ahead:
         return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
                                    lean=False, **ahead)
@@ -316,22 +338,25 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
                             names: bool = True, originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
     trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
-    per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``), ``qc``: see
+    per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``), ``qc``, ``dedup``: see
     ``scan_pair_source_stream``."""
+    from .dedup import need_dedup
     from .read_qc import need_read_qc
     need_read_qc(qc)
+    need_dedup(dedup)
     if isinstance(source, np.ndarray):
         source = ArraySource(source)
     return _scan_source_stream(indexer, (source,), chunk_bytes, max_read_len, names,
                                partial(_scan_records, originals=True) if originals else _scan_records,
                                **({} if read_filter is None else {"read_filter": read_filter}),
                                **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
-                               **({} if qc is None else {"qc": qc}))
+                               **({} if qc is None else {"qc": qc}),
+                               **({} if dedup is None else {"dedup": dedup}))
 
 
 def scan_pair_end_text(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
