@@ -102,6 +102,16 @@ def parser() -> argparse.ArgumentParser:
     dd.add_argument("--dedup-count-only", action="store_true", help="count the duplicates, remove none")
     dd.add_argument("--dedup-max-slots", type=int, default=None, metavar="N", help="the largest hash table, a power "
                     "of two of slots of 20 bytes, default 2^31; a table grows to twice the records offered")
+    um = p.add_argument_group("unique molecular identifiers (off by default; --umi-loc switches them on)")
+    um.add_argument("--umi-loc", choices=("name", "read1", "read2", "per_read"), default=None, help="where the library's "
+                    "UMIs are.  read1, read2, per_read: the first --umi-len bases of read1, of read2 or of both, cut off on "
+                    "the device with --umi-skip bases of spacer behind them, ahead of the adapter trimming; name: behind "
+                    "the last ':' of the read's name.  With --dedup two pairs (reads) are duplicates only when their UMIs "
+                    "are equal too")
+    um.add_argument("--umi-len", type=int, default=None, metavar="N", help="the bases of an inline UMI, 1 to 32 (needs "
+                    "--umi-loc read1, read2 or per_read)")
+    um.add_argument("--umi-skip", type=int, default=None, metavar="N", help="the bases of spacer behind an inline UMI, "
+                    "cut off with it, 0 to 32, default 0 (needs --umi-loc)")
     return p
 
 
@@ -157,6 +167,18 @@ def _dedup(args):
     return Dedup(remove=not args.dedup_count_only, **sizes)
 
 
+def _umi(args):
+    """The ``Umi`` the options ask for, None without ``--umi-loc``; ``ValueError`` for ``--umi-len`` or ``--umi-skip``
+    without it, and for a value out of range."""
+    if args.umi_loc is None:
+        for option, value in (("--umi-len", args.umi_len), ("--umi-skip", args.umi_skip)):
+            if value is not None:
+                raise ValueError("%s needs --umi-loc" % option)
+        return None
+    from .umi import Umi
+    return Umi(args.umi_loc, **{k: v for k, v in (("length", args.umi_len), ("skip", args.umi_skip)) if v is not None})
+
+
 def _missing(args) -> Optional[str]:
     """genefuse.rs:75-84: the first input file that is not there."""
     for f in (args.ref, args.read1, args.read2, args.fusion):
@@ -196,6 +218,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         dedup = _dedup(args)
         if dedup is not None:
             common["dedup"] = dedup
+        umi = _umi(args)
+        if umi is not None:
+            common["umi"] = umi
         if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
@@ -214,7 +239,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from .read_qc import report_json
         counters = (out[0][2] if out else None) if isinstance(out, list) else out[1]
         with open(args.qc_json, "w") as f:
-            f.write(report_json(qc.result(), counters, **({} if dedup is None else {"duplication": dedup.result()})))
+            f.write(report_json(qc.result(), counters, **({} if dedup is None else {"duplication": dedup.result()}),
+                                **({} if umi is None else {"umi": umi})))
     for results in per_csv:
         sys.stdout.write(report_text(results))
     print("# genefuse v%s, time used: %s seconds\n" % (__version__, time.monotonic() - started))

@@ -247,10 +247,13 @@ class Dedup:
                 _lib.for_stream(t, stream)
         self.slots = slots
 
-    def apply(self, indexer, *batches, stream=None):
+    def apply(self, indexer, *batches, stream=None, umi_codes=None):
         """One ``FastqBatch`` (single-end) or two (R1, R2) keyed, looked up and, with ``remove``, emptied of duplicates:
         (batches, totals) — the batches as ``read_filter.filter_reads_device`` leaves them (with ``remove=False`` as
-        they came), ``totals`` the int64[6] device tensor of this call alone.  Asynchronous."""
+        they came), ``totals`` the int64[6] device tensor of this call alone.  ``umi_codes``: the int64[n] device tensor
+        of the records' UMI codes (umi.py), mixed into the keys between the hashing and the table (``umi.mix_keys_device``)
+        — two records are then duplicates when their bases and their UMIs are equal; None (the default): the calls
+        queued are the same as ever.  Asynchronous."""
         import torch
         if len(batches) not in (1, 2):
             raise ValueError("apply takes one batch or a pair of them, not %d" % len(batches))
@@ -260,6 +263,11 @@ class Dedup:
         self._prepare(indexer, n, stream)
         totals = torch.zeros(TOTALS, dtype=torch.int64, device=self._table.keys.device)
         rec_keys = keys_device(indexer, *batches, stream=stream)
+        if umi_codes is not None:
+            from .umi import mix_keys_device
+            if int(umi_codes.numel()) != n:
+                raise ValueError("apply: %d UMI codes for %d records" % (umi_codes.numel(), n))
+            mix_keys_device(indexer, rec_keys, umi_codes, stream)
         rec_slot = insert_device(indexer, rec_keys, self.offered, self._table, totals, stream)
         if self.remove:
             *batches, _ = remove_device(indexer, rec_slot, self.offered, self._table, totals, *batches, stream=stream)

@@ -158,7 +158,8 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 # ---- the scan from files ------------------------------------------------------------------------------------------
 
 def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host",
-                      originals: bool = False, *, read_filter=None, adapter_trim=None, qc=None, dedup=None):
+                      originals: bool = False, *, read_filter=None, adapter_trim=None, qc=None, dedup=None,
+                      umi=None):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
@@ -173,7 +174,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     ``adapter_trim``: an ``AdapterTrim``, the same for the adapter trimming ahead of the read filter; its totals stand in
     front of the read filter's.  ``qc``: a ``ReadQc``, every chunk's records are measured once, before and behind the
     two (``scan_stream._scan_chunk``), never per index.  ``dedup``: a ``Dedup``, every chunk's records are
-    deduplicated once, behind the read filter; every index reports the same four totals behind the read filter's."""
+    deduplicated once, behind the read filter; every index reports the same four totals behind the read filter's.
+    ``umi``: a ``Umi``, every chunk's records are tagged once, ahead of the trimming (``scan_stream._scan_chunk``); every
+    index reports the same five totals in front of the trimming's."""
     from . import scan_pack, scan_stream
     from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .dedup import DEDUP_COUNTER_KEYS
@@ -181,14 +184,15 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     from .fusion_mapper import FusionMapper
     from .read_pair import finish_pair_hits
     from .scan import named_from_device, route_counters
+    from .umi import UMI_COUNTER_KEYS
     single = len(files) == 1
     count_key = "reads" if single else "pairs"
     first_caps = {} if hits_cap is None else dict(hits_cap=int(hits_cap))
     mappers = [FusionMapper(ix) for ix in indexers]
     found = [[] for _ in indexers]
     sums = [{count_key: 0, "merged_pairs": 0, "retried_reads": 0} for _ in indexers]
-    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS) \
-        + (() if dedup is None else DEDUP_COUNTER_KEYS)
+    extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
+        + (() if read_filter is None else COUNTER_KEYS) + (() if dedup is None else DEDUP_COUNTER_KEYS)
     for t in sums:
         t.update(dict.fromkeys(extra, 0))
     chunks = 0
@@ -235,7 +239,8 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
                                                          **({} if adapter_trim is None else
                                                             {"adapter_trim": adapter_trim}),
                                                          **({} if qc is None else {"qc": qc}),
-                                                         **({} if dedup is None else {"dedup": dedup})):
+                                                         **({} if dedup is None else {"dedup": dedup}),
+                                                         **({} if umi is None else {"umi": umi})):
             for k, (rec, hb, hq, names, tot, *orig) in enumerate(per_index):
                 found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names, *orig)
                 for key in sums[k]:
@@ -254,7 +259,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
                           hits_cap: int = None, inflate: str = "host", tail: str = "host", originals: bool = False,
                           html_file: str = "", *, read_filter=None, adapter_trim=None,
-                          qc=None, dedup=None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          qc=None, dedup=None, umi=None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -295,10 +300,15 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
     ``dedup``: None or a ``dedup.Dedup``, duplicate records removed behind the read filter
     (``scan.scan_pair_end_files``): once as well — a list of CSVs is deduplicated once — and every CSV reports the same
-    four totals."""
+    four totals.
+
+    ``umi``: None or a ``umi.Umi``, the UMIs cut off the reads or read from their names ahead of the trimming and
+    keyed into ``dedup`` (``scan.scan_pair_end_files``): once as well — a list of CSVs is tagged once — and every CSV
+    reports the same five totals.  Without ``read2_file`` "read2" raises ``ValueError``."""
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .fastq import FastqReader, FastqReaderPair
+    from .umi import need_umi
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
     from .report_tail import need_tail
@@ -306,12 +316,14 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     need_read_filter(read_filter)
     need_read_qc(qc)
     need_dedup(dedup)
+    if need_umi(umi) is not None:
+        umi.need_sides(2 if read2_file else 1)
     if need_adapter_trim(adapter_trim) is not None and not read2_file and not adapter_trim.adapter_r1:
         raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     from .fusion_mapper import FusionMapper
     from .indexer import Fusion
-    from .scan import (GeneSlices, _route_inflate, deduplicated_reads, filtered_reads, finish_matches, measured_reads, open_index,
-                       pairs_found, read_contigs, report_matches, single_end_found, trimmed_reads)
+    from .scan import (GeneSlices, _cuts, _route_inflate, deduplicated_reads, filtered_reads, finish_matches, measured_reads,
+                       open_index, pairs_found, read_contigs, report_matches, single_end_found, tagged_reads, trimmed_reads)
     settings = settings or Settings()
     fq_inflate, ref_inflate = _route_inflate(inflate, chunk_bytes, ref_chunk_bytes)
     csvs = read_csv_list(csv_list_file)
@@ -338,7 +350,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                           **({} if read_filter is None else {"read_filter": read_filter}),
                                           **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
                                           **({} if qc is None else {"qc": qc}),
-                                          **({} if dedup is None else {"dedup": dedup}))
+                                          **({} if dedup is None else {"dedup": dedup}),
+                                          **({} if umi is None else {"umi": umi}))
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
@@ -347,17 +360,19 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
         for k, (_, results, _) in enumerate(out):
             write(k, results)
         return out
-    reads = prepared = counted = trimmed = deduplicated = None
+    reads = prepared = counted = trimmed = deduplicated = tagged = None
     for k, csv in enumerate(csvs):
         with open_index(refs[k], csv, device) as (ix, fusions):
             if reads is None:   # (the first index names the device the records go to)
                 if read2_file:
                     (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
                     measured_reads(ix, qc, "before", l, r)
+                    (l, r), codes, tagged = tagged_reads(ix, umi, ltext, l, r)
                     (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
                     (l, r), counted = filtered_reads(ix, read_filter, l, r)
-                    (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r)
-                    if adapter_trim is not None or read_filter is not None or dedup is not None:
+                    (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r,
+                                                              **({} if codes is None else {"umi_codes": codes}))
+                    if adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi):
                         measured_reads(ix, qc, "after", l, r)
                     reads = (l, ltext), (r, rtext)
                     prepared = prepare_pairs_device(ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets,
@@ -365,10 +380,11 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                 else:
                     b, text = FastqReader(read1_file).read_all_device(ix)
                     measured_reads(ix, qc, "before", b)
+                    (b,), codes, tagged = tagged_reads(ix, umi, text, b)
                     (b,), trimmed = trimmed_reads(ix, adapter_trim, b)
                     (b,), counted = filtered_reads(ix, read_filter, b)
-                    (b,), deduplicated = deduplicated_reads(ix, dedup, b)
-                    if adapter_trim is not None or read_filter is not None or dedup is not None:
+                    (b,), deduplicated = deduplicated_reads(ix, dedup, b, **({} if codes is None else {"umi_codes": codes}))
+                    if adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi):
                         measured_reads(ix, qc, "after", b)
                     reads = b, text
             mapper = FusionMapper(ix)
@@ -377,7 +393,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                        lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps), originals)
             else:
                 produced = single_end_found(ix, mapper, *reads, originals)
-            produced = deduplicated(counted(trimmed(produced)))
+            produced = deduplicated(counted(trimmed(tagged(produced))))
             kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:],
                                             tail=tail)
             results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)
@@ -390,7 +406,8 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
                 settings: Settings = None, json_file: str = "", command: str = "", version: str = "", time: str = "",
                 chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
                 originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False, *,
-                alignable_filter: str = None, read_filter=None, adapter_trim=None, qc=None, dedup=None):
+                alignable_filter: str = None, read_filter=None, adapter_trim=None, qc=None, dedup=None,
+                umi=None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -409,13 +426,16 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     ``adapter_trim.AdapterTrim``, adapter trimming ahead of the read filter, in every mode, handed on only when set.
     ``qc``: None or a ``read_qc.ReadQc``, the reads measured before and behind the two, in every mode, handed on only
     when set; for a list of CSVs the reads are measured once.  ``dedup``: None or a ``dedup.Dedup``, duplicate records
-    removed behind the read filter, in every mode, handed on only when set; a list of CSVs is deduplicated once."""
+    removed behind the read filter, in every mode, handed on only when set; a list of CSVs is deduplicated once.
+    ``umi``: None or a ``umi.Umi``, the UMIs cut off or read from the names ahead of the trimming and keyed into ``dedup``,
+    in every mode, handed on only when set; a list of CSVs is tagged once."""
     from . import scan
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .alignable import need_filter
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
+    from .umi import need_umi
     filtered = {} if need_read_filter(read_filter) is None else {"read_filter": read_filter}
     if need_adapter_trim(adapter_trim) is not None:
         filtered["adapter_trim"] = adapter_trim
@@ -423,6 +443,8 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         filtered["qc"] = qc
     if need_dedup(dedup) is not None:
         filtered["dedup"] = dedup
+    if need_umi(umi) is not None:
+        filtered["umi"] = umi
     if need_filter(alignable_filter, remove_alignables) and _rust_stem_ext(fusion_file)[2] != "csv":
         raise ValueError("alignable_filter: only the scans of one CSV have this filter")
     if remove_alignables and not (_rust_stem_ext(fusion_file)[2] == "csv" and read2_file):

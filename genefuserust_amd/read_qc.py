@@ -240,14 +240,21 @@ ADAPTER_CUTTING = (("adapter_trimmed_reads", "adapter_reads_cut"), ("adapter_tri
                    ("overlapping_pairs", "adapter_overlapping_pairs"))
 
 
-def report_document(result: QcResult, counters: Optional[dict] = None, duplication=None) -> dict:
+UMI_COUNTS = (("tagged_reads", "umi_reads_tagged"), ("reads_without_umi", "umi_missing"), ("umis_with_N", "umi_with_n"),
+              ("cut_bases", "umi_bases_cut"), ("too_short_reads", "umi_too_short"))
+
+
+def report_document(result: QcResult, counters: Optional[dict] = None, duplication=None, umi=None) -> dict:
     """The QC document as a dict, in the order ``report_json`` writes it.  ``duplication``: the ``DedupResult`` of the
-    scan's ``Dedup``."""
+    scan's ``Dedup``.  ``umi``: the scan's ``Umi``."""
     doc = {"summary": {"before_filtering": result.summary("before"), "after_filtering": result.summary("after")}}
     if counters is not None and "reads_passed" in counters:
         doc["filtering_result"] = {name: int(counters[key]) for name, key in FILTERING_RESULT}
     if counters is not None and "adapter_reads_cut" in counters:
         doc["adapter_cutting"] = {name: int(counters[key]) for name, key in ADAPTER_CUTTING}
+    if counters is not None and "umi_reads_tagged" in counters:
+        doc["umi"] = {**({} if umi is None else umi.describe()),
+                      **{name: int(counters[key]) for name, key in UMI_COUNTS}}
     if duplication is not None:
         doc["duplication"] = {"rate": _rate(int(duplication.duplicates), int(duplication.checked)),
                               "histogram": [int(x) for x in duplication.histogram[1:]]}
@@ -260,13 +267,14 @@ def report_document(result: QcResult, counters: Optional[dict] = None, duplicati
     return doc
 
 
-def report_json(result: QcResult, counters: Optional[dict] = None, duplication=None) -> str:
+def report_json(result: QcResult, counters: Optional[dict] = None, duplication=None, umi=None) -> str:
     """This project's own QC document, with fastp's key names where the statistic is the same: ``summary`` with
     ``before_filtering`` / ``after_filtering`` (``QcResult.summary``); with ``counters`` of a scan that ran them
-    ``filtering_result`` (the read filter's counts) and ``adapter_cutting`` (the trimming's); with ``duplication``, a
+    ``filtering_result`` (the read filter's counts), ``adapter_cutting`` (the trimming's) and ``umi`` (the UMI step's five
+    counts, and with ``umi``, the scan's ``umi.Umi``, its ``source``, ``length`` and ``skip`` in front); with ``duplication``, a
     ``dedup.DedupResult``, ``duplication``: the ``rate``, duplicates over the records checked (0.0 over 0), and the
     ``histogram``, entry c - 1 the keys offered c times, the last one those offered 31 times or more; ``insert_size``
     (``QcResult.insert_size``) when it was taken; and ``read1_before_filtering``, ``read2_before_filtering``,
     ``read1_after_filtering``, ``read2_after_filtering`` (``QcResult.curves``; read2 with pairs).  Compatibility with
     an outside parser is not claimed."""
-    return json.dumps(report_document(result, counters, duplication), indent=1) + "\n"
+    return json.dumps(report_document(result, counters, duplication, umi), indent=1) + "\n"

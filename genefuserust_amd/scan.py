@@ -127,16 +127,46 @@ def filtered_reads(ix: Indexer, read_filter, *batches):
     return tuple(kept), counted
 
 
-def deduplicated_reads(ix: Indexer, dedup, *batches):
+def tagged_reads(ix: Indexer, umi, text: bytes, *batches):
+    """The ``FastqBatch``es (a file's records, or a pair's) through the UMI step on the index's device (umi.py), ahead
+    of ``trimmed_reads``: (the batches it leaves, the records' UMI codes or None, ``counted(produced)``).  An inline
+    source cuts the UMIs off the records; the name source reads them from ``text``, the host text of the file (of R1),
+    which goes to the device once more for it, and leaves the batches as they are.  ``counted`` adds the five ``umi_*``
+    totals to the end of a producer's counters in front of the filter counts — so it is applied first — and ``umi``
+    None gives the batches as they are, no codes, nothing queued, and a ``counted`` that changes nothing."""
+    if umi is None:
+        return batches, None, lambda produced: produced
+    from .umi import cut_umis_device, name_umis_device, umi_totals_counters
+    umi.need_sides(len(batches))
+    if umi.inline:
+        *kept, codes, totals = cut_umis_device(ix, umi, *batches)
+    else:
+        import warnings
+        import torch
+        with warnings.catch_warnings():
+            # (the upload only reads the host text: no copy of it into a writable buffer first)
+            warnings.simplefilter("ignore", UserWarning)
+            d_text = torch.frombuffer(text, dtype=torch.uint8).to(batches[0].bases.device) if text \
+                else torch.empty(0, dtype=torch.uint8, device=batches[0].bases.device)
+        kept, (codes, totals) = batches, name_umis_device(ix, d_text, batches[0])
+
+    def counted(produced):
+        found, before, after = produced
+        return found, {**before, **umi_totals_counters(totals.cpu().tolist())}, after
+    return tuple(kept), codes, counted
+
+
+def deduplicated_reads(ix: Indexer, dedup, *batches, umi_codes=None):
     """The ``FastqBatch``es (a file's records, or a pair's) through the duplicate removal on the index's device
     (dedup.py), behind ``filtered_reads`` and in front of the scan: (the batches it leaves, ``counted(produced)``).
     ``counted`` adds the four ``dedup_*`` totals to the end of a producer's counters in front of the filter counts — so it
     is applied behind ``filtered_reads``' — and ``dedup`` None gives the batches as they are, nothing queued, and a
-    ``counted`` that changes nothing."""
+    ``counted`` that changes nothing.  ``umi_codes``: what ``tagged_reads`` gave, handed to ``Dedup.apply`` only when
+    set."""
     if dedup is None:
         return batches, lambda produced: produced
     from .dedup import dedup_totals_counters
-    kept, totals = dedup.apply(ix, *batches)
+    kept, totals = dedup.apply(ix, *batches, **({} if umi_codes is None else {"umi_codes": umi_codes}))
 
     def counted(produced):
         found, before, after = produced
@@ -254,7 +284,7 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
 
 def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
                    originals: bool = False, *, read_filter=None,
-                   adapter_trim=None, qc=None, dedup=None) -> Tuple[List[ReadMatch], dict, dict]:
+                   adapter_trim=None, qc=None, dedup=None, umi=None) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
     order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
     ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``).
@@ -264,29 +294,32 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     and its five totals stand in front of the read filter's.  ``qc``: a ``ReadQc``, every chunk's records are measured
     before and behind the two (``scan_stream._scan_chunk``); the counters stay as they are.  ``dedup``: a ``Dedup``,
     every chunk's records go through the duplicate removal behind the read filter, and its four totals stand behind
-    the read filter's."""
+    the read filter's.  ``umi``: a ``Umi``, every chunk's records go through the UMI step ahead of the adapter
+    trimming, and its five totals stand in front of the trimming's."""
     from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .dedup import DEDUP_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
     from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
+    from .umi import UMI_COUNTER_KEYS
     count_key = "pairs" if len(files) == 2 else "reads"
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
     found: List[ReadMatch] = []
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
-    extra = (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) + (() if read_filter is None else COUNTER_KEYS) \
-        + (() if dedup is None else DEDUP_COUNTER_KEYS)
+    extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
+        + (() if read_filter is None else COUNTER_KEYS) + (() if dedup is None else DEDUP_COUNTER_KEYS)
     sums.update(dict.fromkeys(extra, 0))
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        # (originals=False, read_filter=None, adapter_trim=None, qc=None and dedup=None are not passed on: the stream is
-        #  then called as it always was)
+        # (originals=False, read_filter=None, adapter_trim=None, qc=None, dedup=None and umi=None are not passed on: the
+        #  stream is then called as it always was)
         for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
                                                      **({"originals": True} if originals else {}),
                                                      **({"read_filter": read_filter} if read_filter is not None else {}),
                                                      **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
                                                      **({"qc": qc} if qc is not None else {}),
-                                                     **({"dedup": dedup} if dedup is not None else {})):
+                                                     **({"dedup": dedup} if dedup is not None else {}),
+                                                     **({"umi": umi} if umi is not None else {})):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
@@ -304,6 +337,11 @@ def _route_inflate(inflate, chunk_bytes, ref_chunk_bytes):
     return (inflate if chunk_bytes is not None else "host"), (inflate if ref_chunk_bytes is not None else "host")
 
 
+def _cuts(umi) -> bool:
+    """Whether the UMI step changes the records: an inline source does, the name source and None do not."""
+    return umi is not None and umi.inline
+
+
 def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) -> None:
     """``ValueError`` for an ``alignable_filter`` that ``finish_matches`` refuses, and for the genome filter with a
     streamed reference: before any file is opened."""
@@ -315,18 +353,20 @@ def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) ->
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
                       chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
-                      alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None, dedup=None):
+                      alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
     from .report_tail import need_tail
+    from .umi import need_umi
     need_tail(tail)
     need_read_filter(read_filter)
     need_adapter_trim(adapter_trim)
     need_read_qc(qc)
     need_dedup(dedup)
+    need_umi(umi)
     _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
@@ -339,20 +379,23 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
                                       **({"read_filter": read_filter} if read_filter is not None else {}),
                                       **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
                                       **({"qc": qc} if qc is not None else {}),
-                                      **({"dedup": dedup} if dedup is not None else {}))
+                                      **({"dedup": dedup} if dedup is not None else {}),
+                                      **({"umi": umi} if umi is not None else {}))
         else:
             (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
             measured_reads(ix, qc, "before", l, r)
+            (l, r), codes, tagged = tagged_reads(ix, umi, ltext, l, r)
             (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
             (l, r), counted = filtered_reads(ix, read_filter, l, r)
-            (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r)
-            if adapter_trim is not None or read_filter is not None or dedup is not None:
+            (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r, **({} if codes is None else {"umi_codes": codes}))
+            if adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi):
                 measured_reads(ix, qc, "after", l, r)
             reads = (l, ltext), (r, rtext)
             max_len = max(l.max_read_len(), r.max_read_len(), 1)
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
-            produced = deduplicated(counted(trimmed(pairs_found(mapper, reads, max_len, lambda **caps: scan_pairs_device(
-                ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals))))
+            produced = deduplicated(counted(trimmed(tagged(pairs_found(
+                mapper, reads, max_len, lambda **caps: scan_pairs_device(
+                    ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)))))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
                                         tail=tail, alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -364,7 +407,7 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         inflate: str = "host", tail: str = "host",
                         originals: bool = False, *, alignable_filter: str = None,
                         read_filter=None, adapter_trim=None, qc=None,
-                        dedup=None) -> Tuple[List[ReadMatch], dict]:
+                        dedup=None, umi=None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -431,11 +474,24 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     measured behind this step.  The counters gain ``dedup_checked``, ``dedup_unique``, ``dedup_duplicates`` and
     ``dedup_bases_removed`` behind the read filter's keys, the same on every route; ``dedup.result()`` has the rate and
     the histogram.  One ``Dedup`` handed to two scans removes the duplicates across them.  ``ValueError`` for anything
-    else.  Without it nothing more is queued or allocated."""
+    else.  Without it nothing more is queued or allocated.
+
+    ``umi``: None (the default), or a ``umi.Umi``: the library's unique molecular identifiers (umi.py), handled on the
+    device between ``qc``'s "before" stage and the adapter trimming.  An inline source ("read1", "read2", "per_read")
+    takes the first ``length`` bases and ``skip`` bases of spacer off the mates it names, so that they are neither
+    merged, nor mapped, nor hashed as genome; a pair with a mate shorter than that is scanned as two empty reads.  The
+    name source reads the UMI behind the last ':' of the first token of R1's name and moves no byte.  With ``dedup``
+    every record's UMI code is mixed into its key: two pairs are duplicates when their bases and their UMIs are equal, a
+    pair without a UMI by its bases alone.  Without ``dedup`` the inline sources still cut, the name source only counts.
+    The record indices stay, so names and ``m_original_reads`` are those of the sequencer.  The counters gain
+    ``umi_reads_tagged``, ``umi_missing``, ``umi_with_n``, ``umi_bases_cut`` and ``umi_too_short`` in front of the
+    adapter trimming's keys, the same on every route.  ``ValueError`` for anything else.  Without it nothing more is
+    queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
                              remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
                              alignable_filter, read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
-                             **({"dedup": dedup} if dedup is not None else {}))[:2]
+                             **({"dedup": dedup} if dedup is not None else {}),
+                             **({"umi": umi} if umi is not None else {}))[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
@@ -443,7 +499,7 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                          inflate: str = "host", tail: str = "host", originals: bool = False,
                          remove_alignables: bool = False, *,
                          alignable_filter: str = None, read_filter=None,
-                         adapter_trim=None, qc=None, dedup=None) -> Tuple[List[FusionResult], dict]:
+                         adapter_trim=None, qc=None, dedup=None, umi=None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
@@ -451,7 +507,8 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
     ``originals`` (what ``report_html`` shows under the supporting reads), ``remove_alignables`` (the reference's last
     filter as it is), ``alignable_filter`` (a last filter that works), ``read_filter`` (a quality filter ahead of the
     scan), ``adapter_trim`` (adapter trimming ahead of that), ``qc`` (the reads measured before and behind the two),
-    ``dedup`` (duplicate pairs removed behind the read filter): see ``scan_pair_end_files``.  ``tail``: "device" also
+    ``dedup`` (duplicate pairs removed behind the read filter), ``umi`` (UMIs cut off ahead of the trimming and keyed
+    into ``dedup``): see ``scan_pair_end_files``.  ``tail``: "device" also
     clusters in bulk — the first fit of all groups in one host call, the refined breaks of all matches in one
     ``gf_rp_adjust_device`` call (report_tail.py); the same results, counters and report bytes."""
     settings = settings or Settings()
@@ -459,23 +516,27 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                                              settings.deletion_threshold, remove_alignables, chunk_bytes,
                                              ref_chunk_bytes, inflate, tail, originals, alignable_filter,
                                              read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
-                                             **({"dedup": dedup} if dedup is not None else {})),
+                                             **({"dedup": dedup} if dedup is not None else {}),
+                                             **({"umi": umi} if umi is not None else {})),
                           settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                         ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None,
-                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None):
+                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .read_filter import need_read_filter
     from .read_qc import need_read_qc
     from .report_tail import need_tail
+    from .umi import need_umi
     need_tail(tail)
     need_read_filter(read_filter)
     need_read_qc(qc)
     need_dedup(dedup)
+    if need_umi(umi) is not None:
+        umi.need_sides(1)
     if need_adapter_trim(adapter_trim) is not None and not adapter_trim.adapter_r1:
         raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     _need_whole_contigs(alignable_filter, False, ref_chunk_bytes)
@@ -491,19 +552,21 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
                                       **({"read_filter": read_filter} if read_filter is not None else {}),
                                       **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
                                       **({"qc": qc} if qc is not None else {}),
-                                      **({"dedup": dedup} if dedup is not None else {}))
+                                      **({"dedup": dedup} if dedup is not None else {}),
+                                      **({"umi": umi} if umi is not None else {}))
         else:   # (both routes start from the records in HBM, where the read filter runs)
             b, text = FastqReader(read1_file).read_all_device(ix)
             measured_reads(ix, qc, "before", b)
+            (b,), codes, tagged = tagged_reads(ix, umi, text, b)
             (b,), trimmed = trimmed_reads(ix, adapter_trim, b)
             (b,), counted = filtered_reads(ix, read_filter, b)
-            (b,), deduplicated = deduplicated_reads(ix, dedup, b)
-            if adapter_trim is not None or read_filter is not None or dedup is not None:
+            (b,), deduplicated = deduplicated_reads(ix, dedup, b, **({} if codes is None else {"umi_codes": codes}))
+            if adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi):
                 measured_reads(ix, qc, "after", b)
             if route == "device":
-                produced = deduplicated(counted(trimmed(single_end_found(ix, mapper, b, text, originals))))
+                produced = deduplicated(counted(trimmed(tagged(single_end_found(ix, mapper, b, text, originals)))))
             else:
-                produced = deduplicated(counted(trimmed(_single_end_host_found(mapper, b, text, originals))))
+                produced = deduplicated(counted(trimmed(tagged(_single_end_host_found(mapper, b, text, originals)))))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, False, *produced[1:], tail=tail,
                                         alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -515,7 +578,7 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           inflate: str = "host", tail: str = "host",
                           originals: bool = False, *, alignable_filter: str = None,
                           read_filter=None, adapter_trim=None, qc=None,
-                        dedup=None) -> Tuple[List[ReadMatch], dict]:
+                          dedup=None, umi=None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -536,11 +599,14 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     either route; ``ValueError`` without ``adapter_r1``; see ``scan_pair_end_files``.  ``qc``: None or a ``ReadQc``,
     the reads measured before and behind the two, on either route (no insert sizes: there are no pairs); see
     ``scan_pair_end_files``.  ``dedup``: None or a ``Dedup``, duplicate reads removed behind the read filter, on either
-    route; see ``scan_pair_end_files``."""
+    route; see ``scan_pair_end_files``.  ``umi``: None or a ``Umi``, the reads' UMIs cut off ("read1", or "per_read",
+    which is the same here) or read from their names ("name") ahead of the trimming and keyed into ``dedup``, on either
+    route; ``ValueError`` for "read2"; see ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                                ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter,
                                adapter_trim, **({"qc": qc} if qc is not None else {}),
-                               **({"dedup": dedup} if dedup is not None else {}))[:2]
+                               **({"dedup": dedup} if dedup is not None else {}),
+                               **({"umi": umi} if umi is not None else {}))[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
@@ -548,9 +614,10 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                            ref_chunk_bytes: int = None, inflate: str = "host",
                            tail: str = "host", originals: bool = False, *,
                            alignable_filter: str = None, read_filter=None,
-                           adapter_trim=None, qc=None, dedup=None) -> Tuple[List[FusionResult], dict]:
+                           adapter_trim=None, qc=None, dedup=None, umi=None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
-    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``, ``qc``, ``dedup``: see
+    ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``, ``qc``, ``dedup``,
+    ``umi``: see
     ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
@@ -558,4 +625,5 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                                                route, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
                                                alignable_filter, read_filter, adapter_trim,
                                                **({"qc": qc} if qc is not None else {}),
-                                               **({"dedup": dedup} if dedup is not None else {})), settings, tail, device)
+                                               **({"dedup": dedup} if dedup is not None else {}),
+                                               **({"umi": umi} if umi is not None else {})), settings, tail, device)

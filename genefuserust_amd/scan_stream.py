@@ -5,7 +5,8 @@ list happens on the device, chunk k+1 being read and crossing the link while chu
 
     byte source (a file, gunzipped as it is read; a text in memory)  --readinto, upload threads-->  pinned staging
     block  --H2D, copy stream-->  device text buffer (behind the carried-over tail of the previous chunk)  -->
-    gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_at_trim_device, the adapter trimming, and
+    gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_um_cut_device or gf_um_names_device, the UMIs,
+    gf_at_trim_device, the adapter trimming, and
     gf_pp_filter_device, the read filter, and the gf_dd_* calls, the duplicate removal)  -->
     gf_scan_pairs_device (merge, map, reverse-complement
     retries, ordered compaction) or gf_se_scan_device  -->  gf_hn_names_device (the names of the hit records; on
@@ -174,12 +175,28 @@ def _trim_chunk(indexer: Indexer, adapter_trim, batches, m: int):
     return kept, totals
 
 
-def _dedup_chunk(indexer: Indexer, dedup, batches, m: int):
+def _dedup_chunk(indexer: Indexer, dedup, batches, m: int, umi_codes=None):
     """The first ``m`` records of every side through the duplicate removal (dedup.py), queued behind ``_filter_chunk``:
     (the batches it leaves, of ``m`` records each; its totals, on the device).  Only these ``m`` are offered to the
     table: the records behind them are carried to the next chunk and offered there, once, so that the indices the table
-    counts are the files'."""
-    return dedup.apply(indexer, *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches])
+    counts are the files'.  ``umi_codes``: what ``_umi_chunk`` gave for these ``m`` records, handed on only when set."""
+    return dedup.apply(indexer, *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches],
+                       **({} if umi_codes is None else {"umi_codes": umi_codes}))
+
+
+def _umi_chunk(indexer: Indexer, umi, texts, batches, m: int):
+    """The first ``m`` records of every side through the UMI step (umi.py), queued behind the cut and ahead of
+    ``_trim_chunk``: (the batches it leaves; the ``m`` codes; its totals, on the device).  An inline source cuts the
+    UMIs off — the batches then hold ``m`` records each; the name source reads the codes from the chunk's text (R1's)
+    and leaves the batches as they are.  Only these ``m`` records are tagged: the ones behind them are carried to the
+    next chunk and tagged there, once."""
+    from .umi import cut_umis_device, name_umis_device
+    if umi.inline:
+        *kept, codes, totals = cut_umis_device(indexer, umi,
+                                               *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches])
+        return kept, codes, totals
+    codes, totals = name_umis_device(indexer, texts[0], batches[0]._replace(n_records=m))
+    return batches, codes, totals
 
 
 def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
@@ -190,7 +207,7 @@ def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
 
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
                 scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None,
-                qc=None, dedup=None):
+                qc=None, dedup=None, umi=None):
     """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
     ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
     ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do).  ``read_filter``: a
@@ -202,9 +219,13 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     records of every side — the rest are carried into the next chunk and measured there — are added to its tables
     between the cut, the full one again, and the trimming, and behind the last of the steps when any of them runs.
     ``dedup``: a ``Dedup``, the same for the duplicate removal, which runs last, behind the read filter — the full cut
-    again; its totals go under ``dedup.DEDUP_COUNTER_KEYS``, behind the read filter's."""
+    again; its totals go under ``dedup.DEDUP_COUNTER_KEYS``, behind the read filter's.  ``umi``: a ``Umi``, the UMI
+    step (``_umi_chunk``) between ``qc``'s "before" stage and the trimming — an inline source needs the full cut, the
+    name source alone does not; the codes it gives go to the duplicate removal, and its totals under
+    ``umi.UMI_COUNTER_KEYS``, in front of the trimming's."""
     from .fastq import fastq_cut_device
-    if read_filter is not None or adapter_trim is not None or qc is not None or dedup is not None:
+    umi_cuts = umi is not None and umi.inline
+    if read_filter is not None or adapter_trim is not None or qc is not None or dedup is not None or umi_cuts:
         lean = False
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
@@ -213,8 +234,11 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     m, counts, cuts = _record_cuts(batches, texts, final, side_names)
     if qc is not None and m > 0:
         _measure_chunk(indexer, qc, "before", batches, m)
-    if (read_filter is not None or adapter_trim is not None or dedup is not None) and m > 0:
+    if (read_filter is not None or adapter_trim is not None or dedup is not None or umi is not None) and m > 0:
         kept, counted = batches, {}
+        if umi is not None:
+            from .umi import umi_totals_counters
+            kept, umi_codes, umi_totals = _umi_chunk(indexer, umi, texts, kept, m)
         if adapter_trim is not None:
             from .adapter_trim import adapter_totals_counters
             kept, trim_totals = _trim_chunk(indexer, adapter_trim, kept, m)
@@ -223,10 +247,14 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
             kept, totals = _filter_chunk(indexer, read_filter, kept, m)
         if dedup is not None:
             from .dedup import dedup_totals_counters
-            kept, dedup_totals = _dedup_chunk(indexer, dedup, kept, m)
-        if qc is not None:
+            kept, dedup_totals = _dedup_chunk(indexer, dedup, kept, m,
+                                              **({} if umi is None else {"umi_codes": umi_codes}))
+        # (the name source moves no byte: alone it leaves nothing to measure "after", as on the whole-file routes)
+        if qc is not None and (read_filter is not None or adapter_trim is not None or dedup is not None or umi_cuts):
             _measure_chunk(indexer, qc, "after", kept, m)
         out = scan_records(indexer, texts, kept, m, done, max_read_len, names)
+        if umi is not None:
+            counted.update(umi_totals_counters(umi_totals.cpu().tolist()))
         if adapter_trim is not None:
             counted.update(adapter_totals_counters(trim_totals.cpu().tolist()))
         if read_filter is not None:
@@ -246,12 +274,12 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
                         scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None,
-                        adapter_trim=None, qc=None, dedup=None):
+                        adapter_trim=None, qc=None, dedup=None, umi=None):
     """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
     for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
     of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``).  ``read_filter``: a ``ReadFilter``, handed
     to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise; ``qc``: a ``ReadQc``, likewise;
-    ``dedup``: a ``Dedup``, likewise."""
+    ``dedup``: a ``Dedup``, likewise; ``umi``: a ``Umi``, likewise."""
     import torch
     filtered = {} if read_filter is None else {"read_filter": read_filter}
     if adapter_trim is not None:
@@ -260,6 +288,8 @@ def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_le
         filtered["qc"] = qc
     if dedup is not None:
         filtered["dedup"] = dedup
+    if umi is not None:
+        filtered["umi"] = umi
     h = indexer._handle()
 
     def copy(ptr: int, dst: int, n: int, stream: int) -> None:
@@ -293,7 +323,8 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320, names: bool = True,
                             originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None, dedup=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None,
+                            umi=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
@@ -313,16 +344,24 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     behind the read filter when either of the two runs; what is yielded stays as it is.  None (the default): nothing
     more is queued.  ``dedup``: a ``dedup.Dedup``, every chunk's pairs go through the duplicate removal behind the read
     filter — the full cut again — and ``qc``'s "after" stage moves behind it; the chunk's totals gain its four counts
-    (``dedup.DEDUP_COUNTER_KEYS``).  None (the default): nothing more is queued.  ``ValueError`` for anything else."""
+    (``dedup.DEDUP_COUNTER_KEYS``).  None (the default): nothing more is queued.  ``umi``: a ``umi.Umi``, every chunk's
+    pairs go through the UMI step between ``qc``'s "before" stage and the trimming: an inline source cuts the UMIs off
+    — the full cut again — the name source reads them from R1's names in the chunk's text; the codes go to ``dedup``,
+    and the chunk's totals gain its five counts (``umi.UMI_COUNTER_KEYS``) in front of the trimming's.  A chunk tags
+    the pairs it scans, never the ones it carries over.  None (the default): nothing more is queued.  ``ValueError``
+    for anything else."""
     from .dedup import need_dedup
     from .read_qc import need_read_qc
+    from .umi import need_umi
     scan_records = partial(_scan_records, originals=True) if originals else _scan_records
+    need_umi(umi)
     ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim),
                                ("qc", need_read_qc(qc)), ("dedup", need_dedup(dedup))) if v is not None}
-    if ahead:
+    if ahead or (umi is not None and umi.inline):
         return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
-                                   lean=False, **ahead)
-    return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records)
+                                   lean=False, **ahead, **({} if umi is None else {"umi": umi}))
+    return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
+                               **({} if umi is None else {"umi": umi}))
 
 
 def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
@@ -338,17 +377,21 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
                             names: bool = True, originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None, dedup=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None,
+                            umi=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
     trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
     per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``), ``qc``, ``dedup``: see
-    ``scan_pair_source_stream``."""
+    ``scan_pair_source_stream``.  ``umi``: likewise; "per_read" is "read1" here, and "read2" raises ``ValueError``."""
     from .dedup import need_dedup
     from .read_qc import need_read_qc
+    from .umi import need_umi
     need_read_qc(qc)
     need_dedup(dedup)
+    if need_umi(umi) is not None:
+        umi.need_sides(1)
     if isinstance(source, np.ndarray):
         source = ArraySource(source)
     return _scan_source_stream(indexer, (source,), chunk_bytes, max_read_len, names,
@@ -356,7 +399,8 @@ def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 
                                **({} if read_filter is None else {"read_filter": read_filter}),
                                **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
                                **({} if qc is None else {"qc": qc}),
-                               **({} if dedup is None else {"dedup": dedup}))
+                               **({} if dedup is None else {"dedup": dedup}),
+                               **({} if umi is None else {"umi": umi}))
 
 
 def scan_pair_end_text(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
