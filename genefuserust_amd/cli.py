@@ -6,7 +6,7 @@ the scan runs (``multi_csv_scan.scan_report``: one CSV or a list of them, paired
 the JSON report are written, the text result is printed, then the closing line.  What this project adds is spelled
 out: the device, the streamed routes, where ``.gz`` files are inflated, where the report tail runs, the
 whole-genome alignable filter, the adapter trimming, the quality filter and the duplicate removal of the reads ahead of
-the scan, and the QC report of the reads.
+the scan, the QC report of the reads, and the cleaned reads written out as FASTQ files.
 """
 from __future__ import annotations
 
@@ -112,7 +112,20 @@ def parser() -> argparse.ArgumentParser:
                     "--umi-loc read1, read2 or per_read)")
     um.add_argument("--umi-skip", type=int, default=None, metavar="N", help="the bases of spacer behind an inline UMI, "
                     "cut off with it, 0 to 32, default 0 (needs --umi-loc)")
+    wr = p.add_argument_group("the cleaned reads as FASTQ files (off by default; --out1 switches them on)")
+    wr.add_argument("--out1", default=None, metavar="FILE", help="write the reads (of read1) that are left with bases "
+                    "behind the steps above there, formatted on the device; .gz: compressed by the host's zlib.  "
+                    "Streams the FASTQ files: without --chunk-bytes in chunks of 128 MiB")
+    wr.add_argument("--out2", default=None, metavar="FILE", help="the same for read2; needed with -2, and a pair is "
+                    "written only when both mates are left with bases (needs --out1)")
+    wr.add_argument("--umi-in-name", action="store_true", help="write the inline UMI that --umi-loc read1, read2 or "
+                    "per_read cuts off into the names, as :UMI at the end of the first token (needs --out1)")
+    wr.add_argument("--out-compression", type=int, default=None, metavar="N", help="zlib's level for .gz outputs, 1 to "
+                    "9, default 4 (needs --out1)")
     return p
+
+
+DEFAULT_OUT_CHUNK_BYTES = 128 << 20   # what --out1 streams with when --chunk-bytes is not given
 
 
 READ_FILTER_OPTIONS = ("qualified_phred", "unqualified_percent", "n_base_limit", "length_required", "cut_tail_window",
@@ -179,6 +192,20 @@ def _umi(args):
     return Umi(args.umi_loc, **{k: v for k, v in (("length", args.umi_len), ("skip", args.umi_skip)) if v is not None})
 
 
+def _read_writer(args):
+    """The ``ReadWriter`` the options ask for, None without ``--out1``; ``ValueError`` for one of the other three
+    without it, and for a value out of range."""
+    if args.out1 is None:
+        for option, given in (("--out2", args.out2 is not None), ("--umi-in-name", args.umi_in_name),
+                              ("--out-compression", args.out_compression is not None)):
+            if given:
+                raise ValueError("%s needs --out1" % option)
+        return None
+    from .read_write import ReadWriter
+    return ReadWriter(args.out1, args.out2, umi_in_name=args.umi_in_name,
+                      **({} if args.out_compression is None else {"compress_level": args.out_compression}))
+
+
 def _missing(args) -> Optional[str]:
     """genefuse.rs:75-84: the first input file that is not there."""
     for f in (args.ref, args.read1, args.read2, args.fusion):
@@ -221,7 +248,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         umi = _umi(args)
         if umi is not None:
             common["umi"] = umi
-        if _rust_stem_ext(args.fusion)[2] != "csv" and args.chunk_bytes is not None:
+        write_reads = _read_writer(args)
+        if write_reads is not None:   # (the records are written by the streamed routes)
+            common["write_reads"] = write_reads
+            if common["chunk_bytes"] is None:
+                common["chunk_bytes"] = DEFAULT_OUT_CHUNK_BYTES
+        if _rust_stem_ext(args.fusion)[2] != "csv" and common["chunk_bytes"] is not None:
             if args.remove_alignables:
                 raise ValueError("remove_alignables: only the paired-end scan of one CSV has this filter")
             if args.alignable_filter is not None:

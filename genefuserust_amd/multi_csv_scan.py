@@ -159,7 +159,7 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host",
                       originals: bool = False, *, read_filter=None, adapter_trim=None, qc=None, dedup=None,
-                      umi=None):
+                      umi=None, write_reads=None):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
@@ -176,7 +176,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     two (``scan_stream._scan_chunk``), never per index.  ``dedup``: a ``Dedup``, every chunk's records are
     deduplicated once, behind the read filter; every index reports the same four totals behind the read filter's.
     ``umi``: a ``Umi``, every chunk's records are tagged once, ahead of the trimming (``scan_stream._scan_chunk``); every
-    index reports the same five totals in front of the trimming's."""
+    index reports the same five totals in front of the trimming's.  ``write_reads``: a ``ReadWriter``, every chunk's
+    records that are left with bases are written once, whatever the number of indexes; every index reports the same three
+    totals behind the duplicate removal's."""
     from . import scan_pack, scan_stream
     from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .dedup import DEDUP_COUNTER_KEYS
@@ -193,6 +195,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     sums = [{count_key: 0, "merged_pairs": 0, "retried_reads": 0} for _ in indexers]
     extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
         + (() if read_filter is None else COUNTER_KEYS) + (() if dedup is None else DEDUP_COUNTER_KEYS)
+    if write_reads is not None:
+        from .read_write import WRITE_COUNTER_KEYS
+        extra += WRITE_COUNTER_KEYS
     for t in sums:
         t.update(dict.fromkeys(extra, 0))
     chunks = 0
@@ -240,7 +245,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
                                                             {"adapter_trim": adapter_trim}),
                                                          **({} if qc is None else {"qc": qc}),
                                                          **({} if dedup is None else {"dedup": dedup}),
-                                                         **({} if umi is None else {"umi": umi})):
+                                                         **({} if umi is None else {"umi": umi}),
+                                                         **({} if write_reads is None else
+                                                            {"write_reads": write_reads})):
             for k, (rec, hb, hq, names, tot, *orig) in enumerate(per_index):
                 found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names, *orig)
                 for key in sums[k]:
@@ -259,7 +266,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                           time: str = "", ref_chunk_bytes: int = None, chunk_bytes: int = None,
                           hits_cap: int = None, inflate: str = "host", tail: str = "host", originals: bool = False,
                           html_file: str = "", *, read_filter=None, adapter_trim=None,
-                          qc=None, dedup=None, umi=None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          qc=None, dedup=None, umi=None,
+                          write_reads=None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -304,7 +312,14 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
     ``umi``: None or a ``umi.Umi``, the UMIs cut off the reads or read from their names ahead of the trimming and
     keyed into ``dedup`` (``scan.scan_pair_end_files``): once as well — a list of CSVs is tagged once — and every CSV
-    reports the same five totals.  Without ``read2_file`` "read2" raises ``ValueError``."""
+    reports the same five totals.  Without ``read2_file`` "read2" raises ``ValueError``.
+
+    ``write_reads``: None or a ``read_write.ReadWriter``, the cleaned records written out as FASTQ files
+    (``scan.scan_pair_end_files``): streamed mode only — ``ValueError`` without ``chunk_bytes`` — and once, however many
+    CSVs; every CSV reports the same three totals."""
+    if write_reads is not None:   # (checked first)
+        from .read_write import need_read_writer
+        need_read_writer(write_reads)
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .fastq import FastqReader, FastqReaderPair
@@ -318,6 +333,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     need_dedup(dedup)
     if need_umi(umi) is not None:
         umi.need_sides(2 if read2_file else 1)
+    if write_reads is not None:
+        write_reads.need_route((read1_file, read2_file) if read2_file else (read1_file,), umi, chunk_bytes is not None)
     if need_adapter_trim(adapter_trim) is not None and not read2_file and not adapter_trim.adapter_r1:
         raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     from .fusion_mapper import FusionMapper
@@ -351,7 +368,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                           **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
                                           **({} if qc is None else {"qc": qc}),
                                           **({} if dedup is None else {"dedup": dedup}),
-                                          **({} if umi is None else {"umi": umi}))
+                                          **({} if umi is None else {"umi": umi}),
+                                          **({} if write_reads is None else {"write_reads": write_reads}))
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
@@ -407,7 +425,7 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
                 chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
                 originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False, *,
                 alignable_filter: str = None, read_filter=None, adapter_trim=None, qc=None, dedup=None,
-                umi=None):
+                umi=None, write_reads=None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -428,8 +446,13 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     when set; for a list of CSVs the reads are measured once.  ``dedup``: None or a ``dedup.Dedup``, duplicate records
     removed behind the read filter, in every mode, handed on only when set; a list of CSVs is deduplicated once.
     ``umi``: None or a ``umi.Umi``, the UMIs cut off or read from the names ahead of the trimming and keyed into ``dedup``,
-    in every mode, handed on only when set; a list of CSVs is tagged once."""
+    in every mode, handed on only when set; a list of CSVs is tagged once.  ``write_reads``: None or a
+    ``read_write.ReadWriter``, the cleaned records written out as FASTQ files by the streamed routes, handed on only
+    when set; ``ValueError`` without ``chunk_bytes``."""
     from . import scan
+    if write_reads is not None:   # (checked first)
+        from .read_write import need_read_writer
+        need_read_writer(write_reads)
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .alignable import need_filter
@@ -445,6 +468,9 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         filtered["dedup"] = dedup
     if need_umi(umi) is not None:
         filtered["umi"] = umi
+    if write_reads is not None:
+        write_reads.need_route((read1_file, read2_file) if read2_file else (read1_file,), umi, chunk_bytes is not None)
+        filtered["write_reads"] = write_reads
     if need_filter(alignable_filter, remove_alignables) and _rust_stem_ext(fusion_file)[2] != "csv":
         raise ValueError("alignable_filter: only the scans of one CSV have this filter")
     if remove_alignables and not (_rust_stem_ext(fusion_file)[2] == "csv" and read2_file):

@@ -284,7 +284,8 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
 
 def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
                    originals: bool = False, *, read_filter=None,
-                   adapter_trim=None, qc=None, dedup=None, umi=None) -> Tuple[List[ReadMatch], dict, dict]:
+                   adapter_trim=None, qc=None, dedup=None, umi=None,
+                   write_reads=None) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
     order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
     ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``).
@@ -295,7 +296,9 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     before and behind the two (``scan_stream._scan_chunk``); the counters stay as they are.  ``dedup``: a ``Dedup``,
     every chunk's records go through the duplicate removal behind the read filter, and its four totals stand behind
     the read filter's.  ``umi``: a ``Umi``, every chunk's records go through the UMI step ahead of the adapter
-    trimming, and its five totals stand in front of the trimming's."""
+    trimming, and its five totals stand in front of the trimming's.  ``write_reads``: a ``ReadWriter``, every chunk's
+    records that are left with bases are written to its files, and its three totals stand behind the duplicate
+    removal's."""
     from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .dedup import DEDUP_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
@@ -307,19 +310,24 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
     extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
         + (() if read_filter is None else COUNTER_KEYS) + (() if dedup is None else DEDUP_COUNTER_KEYS)
+    if write_reads is not None:
+        from .read_write import WRITE_COUNTER_KEYS
+        extra += WRITE_COUNTER_KEYS
     sums.update(dict.fromkeys(extra, 0))
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        # (originals=False, read_filter=None, adapter_trim=None, qc=None, dedup=None and umi=None are not passed on: the
-        #  stream is then called as it always was)
+        # (originals=False, read_filter=None, adapter_trim=None, qc=None, dedup=None, umi=None and write_reads=None are
+        #  not passed on: the stream is then called as it always was)
         for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
                                                      **({"originals": True} if originals else {}),
                                                      **({"read_filter": read_filter} if read_filter is not None else {}),
                                                      **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
                                                      **({"qc": qc} if qc is not None else {}),
                                                      **({"dedup": dedup} if dedup is not None else {}),
-                                                     **({"umi": umi} if umi is not None else {})):
+                                                     **({"umi": umi} if umi is not None else {}),
+                                                     **({"write_reads": write_reads} if write_reads is not None
+                                                        else {})):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
@@ -353,8 +361,12 @@ def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) ->
 
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
                       chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
-                      alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None):
+                      alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None,
+                      write_reads=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
+    if write_reads is not None:   # (checked first)
+        from .read_write import need_read_writer
+        need_read_writer(write_reads)
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .read_filter import need_read_filter
@@ -367,6 +379,8 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
     need_read_qc(qc)
     need_dedup(dedup)
     need_umi(umi)
+    if write_reads is not None:
+        write_reads.need_route((read1_file, read2_file), umi, chunk_bytes is not None)
     _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
     if remove_alignables and ref_chunk_bytes is not None:
         raise ValueError("remove_alignables needs whole contigs; ref_chunk_bytes cuts only the gene slices out of the "
@@ -380,7 +394,8 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
                                       **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
                                       **({"qc": qc} if qc is not None else {}),
                                       **({"dedup": dedup} if dedup is not None else {}),
-                                      **({"umi": umi} if umi is not None else {}))
+                                      **({"umi": umi} if umi is not None else {}),
+                                      **({"write_reads": write_reads} if write_reads is not None else {}))
         else:
             (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
             measured_reads(ix, qc, "before", l, r)
@@ -407,7 +422,7 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         inflate: str = "host", tail: str = "host",
                         originals: bool = False, *, alignable_filter: str = None,
                         read_filter=None, adapter_trim=None, qc=None,
-                        dedup=None, umi=None) -> Tuple[List[ReadMatch], dict]:
+                        dedup=None, umi=None, write_reads=None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -486,12 +501,24 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     The record indices stay, so names and ``m_original_reads`` are those of the sequencer.  The counters gain
     ``umi_reads_tagged``, ``umi_missing``, ``umi_with_n``, ``umi_bases_cut`` and ``umi_too_short`` in front of the
     adapter trimming's keys, the same on every route.  ``ValueError`` for anything else.  Without it nothing more is
-    queued or allocated."""
+    queued or allocated.
+
+    ``write_reads``: None (the default), or a ``read_write.ReadWriter``: the pairs whose mates both still have bases
+    behind the last of these steps are written out as FASTQ files (read_write.py), in file order, R1's to ``out1`` and
+    R2's to ``out2`` — the name lines as the sequencer wrote them, the bases and qualities as the steps left them, and
+    with ``umi_in_name`` the inline UMI that ``umi`` cut off as ``:UMI`` at the end of the name's first token.  The text
+    is formatted on the device per chunk, behind ``qc``'s "after" stage and ahead of the scan, and written by a thread
+    per file; a name that ends in ``.gz`` is compressed by the host's zlib.  Streamed routes only: ``ValueError`` without
+    ``chunk_bytes``, for an output that is an input, and for ``umi_in_name`` without an inline ``umi``.  Alone it
+    rewrites the pairs whose mates both have bases.  The counters gain ``written_records``, ``written_bases`` and
+    ``written_bytes`` behind the duplicate removal's keys; matches and the other counters are those of the scan
+    without it.  Without it nothing more is queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
                              remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
                              alignable_filter, read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
                              **({"dedup": dedup} if dedup is not None else {}),
-                             **({"umi": umi} if umi is not None else {}))[:2]
+                             **({"umi": umi} if umi is not None else {}),
+                             **({"write_reads": write_reads} if write_reads is not None else {}))[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
@@ -499,7 +526,8 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                          inflate: str = "host", tail: str = "host", originals: bool = False,
                          remove_alignables: bool = False, *,
                          alignable_filter: str = None, read_filter=None,
-                         adapter_trim=None, qc=None, dedup=None, umi=None) -> Tuple[List[FusionResult], dict]:
+                         adapter_trim=None, qc=None, dedup=None, umi=None,
+                         write_reads=None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
@@ -508,7 +536,8 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
     filter as it is), ``alignable_filter`` (a last filter that works), ``read_filter`` (a quality filter ahead of the
     scan), ``adapter_trim`` (adapter trimming ahead of that), ``qc`` (the reads measured before and behind the two),
     ``dedup`` (duplicate pairs removed behind the read filter), ``umi`` (UMIs cut off ahead of the trimming and keyed
-    into ``dedup``): see ``scan_pair_end_files``.  ``tail``: "device" also
+    into ``dedup``), ``write_reads`` (the cleaned pairs written out as FASTQ files, streamed routes only): see
+    ``scan_pair_end_files``.  ``tail``: "device" also
     clusters in bulk — the first fit of all groups in one host call, the refined breaks of all matches in one
     ``gf_rp_adjust_device`` call (report_tail.py); the same results, counters and report bytes."""
     settings = settings or Settings()
@@ -517,14 +546,18 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                                              ref_chunk_bytes, inflate, tail, originals, alignable_filter,
                                              read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
                                              **({"dedup": dedup} if dedup is not None else {}),
-                                             **({"umi": umi} if umi is not None else {})),
+                                             **({"umi": umi} if umi is not None else {}),
+                                             **({"write_reads": write_reads} if write_reads is not None else {})),
                           settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                         ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None,
-                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None):
+                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None, write_reads=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
+    if write_reads is not None:   # (checked first)
+        from .read_write import need_read_writer
+        need_read_writer(write_reads)
     from .adapter_trim import need_adapter_trim
     from .dedup import need_dedup
     from .read_filter import need_read_filter
@@ -537,6 +570,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
     need_dedup(dedup)
     if need_umi(umi) is not None:
         umi.need_sides(1)
+    if write_reads is not None:
+        write_reads.need_route((read1_file,), umi, chunk_bytes is not None)
     if need_adapter_trim(adapter_trim) is not None and not adapter_trim.adapter_r1:
         raise ValueError("adapter_trim: single-end reads are trimmed by sequence, and this one has no adapter_r1")
     _need_whole_contigs(alignable_filter, False, ref_chunk_bytes)
@@ -553,7 +588,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
                                       **({"adapter_trim": adapter_trim} if adapter_trim is not None else {}),
                                       **({"qc": qc} if qc is not None else {}),
                                       **({"dedup": dedup} if dedup is not None else {}),
-                                      **({"umi": umi} if umi is not None else {}))
+                                      **({"umi": umi} if umi is not None else {}),
+                                      **({"write_reads": write_reads} if write_reads is not None else {}))
         else:   # (both routes start from the records in HBM, where the read filter runs)
             b, text = FastqReader(read1_file).read_all_device(ix)
             measured_reads(ix, qc, "before", b)
@@ -578,7 +614,7 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           inflate: str = "host", tail: str = "host",
                           originals: bool = False, *, alignable_filter: str = None,
                           read_filter=None, adapter_trim=None, qc=None,
-                          dedup=None, umi=None) -> Tuple[List[ReadMatch], dict]:
+                          dedup=None, umi=None, write_reads=None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -601,12 +637,15 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     ``scan_pair_end_files``.  ``dedup``: None or a ``Dedup``, duplicate reads removed behind the read filter, on either
     route; see ``scan_pair_end_files``.  ``umi``: None or a ``Umi``, the reads' UMIs cut off ("read1", or "per_read",
     which is the same here) or read from their names ("name") ahead of the trimming and keyed into ``dedup``, on either
-    route; ``ValueError`` for "read2"; see ``scan_pair_end_files``."""
+    route; ``ValueError`` for "read2"; see ``scan_pair_end_files``.  ``write_reads``: None or a ``ReadWriter`` without
+    ``out2``, the reads that still have bases written to ``out1``, with ``chunk_bytes`` only; see
+    ``scan_pair_end_files``."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                                ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter,
                                adapter_trim, **({"qc": qc} if qc is not None else {}),
                                **({"dedup": dedup} if dedup is not None else {}),
-                               **({"umi": umi} if umi is not None else {}))[:2]
+                               **({"umi": umi} if umi is not None else {}),
+                               **({"write_reads": write_reads} if write_reads is not None else {}))[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
@@ -614,10 +653,11 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                            ref_chunk_bytes: int = None, inflate: str = "host",
                            tail: str = "host", originals: bool = False, *,
                            alignable_filter: str = None, read_filter=None,
-                           adapter_trim=None, qc=None, dedup=None, umi=None) -> Tuple[List[FusionResult], dict]:
+                           adapter_trim=None, qc=None, dedup=None, umi=None,
+                           write_reads=None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
     ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``, ``qc``, ``dedup``,
-    ``umi``: see
+    ``umi``, ``write_reads``: see
     ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
@@ -626,4 +666,6 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                                                alignable_filter, read_filter, adapter_trim,
                                                **({"qc": qc} if qc is not None else {}),
                                                **({"dedup": dedup} if dedup is not None else {}),
-                                               **({"umi": umi} if umi is not None else {})), settings, tail, device)
+                                               **({"umi": umi} if umi is not None else {}),
+                                               **({"write_reads": write_reads} if write_reads is not None else {})),
+                          settings, tail, device)

@@ -7,7 +7,8 @@ list happens on the device, chunk k+1 being read and crossing the link while chu
     block  --H2D, copy stream-->  device text buffer (behind the carried-over tail of the previous chunk)  -->
     gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_um_cut_device or gf_um_names_device, the UMIs,
     gf_at_trim_device, the adapter trimming, and
-    gf_pp_filter_device, the read filter, and the gf_dd_* calls, the duplicate removal)  -->
+    gf_pp_filter_device, the read filter, and the gf_dd_* calls, the duplicate removal, and gf_rw_format_device, the
+    cleaned records as FASTQ text for the output files)  -->
     gf_scan_pairs_device (merge, map, reverse-complement
     retries, ordered compaction) or gf_se_scan_device  -->  gf_hn_names_device (the names of the hit records; on
     request gf_hn_records_device, their whole FASTQ records for the HTML report)  -->
@@ -207,7 +208,7 @@ def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
 
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
                 scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None,
-                qc=None, dedup=None, umi=None):
+                qc=None, dedup=None, umi=None, write_reads=None):
     """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
     ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
     ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do).  ``read_filter``: a
@@ -222,10 +223,17 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     again; its totals go under ``dedup.DEDUP_COUNTER_KEYS``, behind the read filter's.  ``umi``: a ``Umi``, the UMI
     step (``_umi_chunk``) between ``qc``'s "before" stage and the trimming — an inline source needs the full cut, the
     name source alone does not; the codes it gives go to the duplicate removal, and its totals under
-    ``umi.UMI_COUNTER_KEYS``, in front of the trimming's."""
+    ``umi.UMI_COUNTER_KEYS``, in front of the trimming's.  ``write_reads``: a ``ReadWriter`` with its files open, the
+    first ``m`` records of every side as the last step leaves them are formatted as FASTQ text on the device
+    (read_write.py) behind ``qc``'s "after" stage and ahead of the scan — the full cut again, for the names the chunk's
+    texts and the cut's newline index, for ``umi_in_name`` the batches ahead of the UMI cut — and behind the chunk's
+    read-back the text goes to the files' threads; its totals go under ``read_write.WRITE_COUNTER_KEYS``, behind the
+    duplicate removal's.  The records carried over are written with the next chunk, once."""
     from .fastq import fastq_cut_device
     umi_cuts = umi is not None and umi.inline
     if read_filter is not None or adapter_trim is not None or qc is not None or dedup is not None or umi_cuts:
+        lean = False
+    if write_reads is not None:
         lean = False
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
@@ -234,7 +242,8 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     m, counts, cuts = _record_cuts(batches, texts, final, side_names)
     if qc is not None and m > 0:
         _measure_chunk(indexer, qc, "before", batches, m)
-    if (read_filter is not None or adapter_trim is not None or dedup is not None or umi is not None) and m > 0:
+    if (read_filter is not None or adapter_trim is not None or dedup is not None or umi is not None
+            or write_reads is not None) and m > 0:
         kept, counted = batches, {}
         if umi is not None:
             from .umi import umi_totals_counters
@@ -252,6 +261,9 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
         # (the name source moves no byte: alone it leaves nothing to measure "after", as on the whole-file routes)
         if qc is not None and (read_filter is not None or adapter_trim is not None or dedup is not None or umi_cuts):
             _measure_chunk(indexer, qc, "after", kept, m)
+        if write_reads is not None:
+            formatted = write_reads.format_chunk(indexer, texts, batches, kept, m,
+                                                 **({"pre": batches, "umi": umi} if write_reads.umi_in_name else {}))
         out = scan_records(indexer, texts, kept, m, done, max_read_len, names)
         if umi is not None:
             counted.update(umi_totals_counters(umi_totals.cpu().tolist()))
@@ -261,6 +273,8 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
             counted.update(totals_counters(totals.cpu().tolist()))
         if dedup is not None:
             counted.update(dedup_totals_counters(dedup_totals.cpu().tolist(), dedup.remove))
+        if write_reads is not None:   # (behind the chunk's read-back: the text is ready, and the copy waits for nothing)
+            counted.update(write_reads.collect(formatted))
         for per_index in (out if isinstance(out, list) else [out]):
             per_index[4].update(counted)
     else:
@@ -274,12 +288,14 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
                         scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None,
-                        adapter_trim=None, qc=None, dedup=None, umi=None):
+                        adapter_trim=None, qc=None, dedup=None, umi=None, write_reads=None):
     """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
     for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
     of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``).  ``read_filter``: a ``ReadFilter``, handed
     to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise; ``qc``: a ``ReadQc``, likewise;
-    ``dedup``: a ``Dedup``, likewise; ``umi``: a ``Umi``, likewise."""
+    ``dedup``: a ``Dedup``, likewise; ``umi``: a ``Umi``, likewise.  ``write_reads``: a ``ReadWriter``, likewise; its
+    files are opened before the first chunk, renamed to their names when the stream ends, and removed when it raises or
+    is closed early."""
     import torch
     filtered = {} if read_filter is None else {"read_filter": read_filter}
     if adapter_trim is not None:
@@ -290,21 +306,32 @@ def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_le
         filtered["dedup"] = dedup
     if umi is not None:
         filtered["umi"] = umi
+    if write_reads is not None:
+        filtered["write_reads"] = write_reads
+        write_reads.open(len(sources))
     h = indexer._handle()
 
     def copy(ptr: int, dst: int, n: int, stream: int) -> None:
         _lib.check(_lib.lib().gf_copy_from_host_device(h, ptr, dst, n, stream))
-    stream = ChunkStream(sources, chunk_bytes, torch.device("cuda", indexer.info()["device"]), copy, fill_read_sizes)
-    side_names = [s.name for s in stream.sides]
-    done = 0
-    with closing(stream.run(lambda texts, final: _scan_chunk(indexer, side_names, texts, final, done, max_read_len,
-                                                             names, scan_records, lean, **filtered))) as chunks:
-        for out, m, last in chunks:
-            if out is not None:
-                yield out
-            done += m
-            if last:
-                break
+    try:
+        stream = ChunkStream(sources, chunk_bytes, torch.device("cuda", indexer.info()["device"]), copy,
+                             fill_read_sizes)
+        side_names = [s.name for s in stream.sides]
+        done = 0
+        with closing(stream.run(lambda texts, final: _scan_chunk(indexer, side_names, texts, final, done, max_read_len,
+                                                                 names, scan_records, lean, **filtered))) as chunks:
+            for out, m, last in chunks:
+                if out is not None:
+                    yield out
+                done += m
+                if last:
+                    break
+    except BaseException:   # (a stream that is closed early too: half a file is no output)
+        if write_reads is not None:
+            write_reads.abort()
+        raise
+    if write_reads is not None:
+        write_reads.finish()
 
 
 def open_fastq_sources(opened, files, inflate: str = "host") -> list:
@@ -323,8 +350,8 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320, names: bool = True,
                             originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None, dedup=None,
-                            umi=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None, umi=None,
+                            write_reads=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
@@ -348,15 +375,24 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     pairs go through the UMI step between ``qc``'s "before" stage and the trimming: an inline source cuts the UMIs off
     — the full cut again — the name source reads them from R1's names in the chunk's text; the codes go to ``dedup``,
     and the chunk's totals gain its five counts (``umi.UMI_COUNTER_KEYS``) in front of the trimming's.  A chunk tags
-    the pairs it scans, never the ones it carries over.  None (the default): nothing more is queued.  ``ValueError``
-    for anything else."""
+    the pairs it scans, never the ones it carries over.  None (the default): nothing more is queued.  ``write_reads``:
+    a ``read_write.ReadWriter`` with ``out2``, every chunk's pairs that still have bases in both mates behind the last
+    of these steps are formatted as FASTQ text on the device — the full cut again — and written to its two files by a
+    thread each; the chunk's totals gain its three counts (``read_write.WRITE_COUNTER_KEYS``) behind the duplicate
+    removal's.  A chunk writes the pairs it scans, never the ones it carries over; the files get their names when the
+    stream ends and are removed when it raises.  Alone it rewrites the pairs whose mates both have bases.  None (the
+    default): nothing more is queued.  ``ValueError`` for anything else."""
     from .dedup import need_dedup
     from .read_qc import need_read_qc
     from .umi import need_umi
+    if write_reads is not None:   # (checked first)
+        from .read_write import need_read_writer
+        need_read_writer(write_reads).need_route(("R1", "R2"), need_umi(umi))
     scan_records = partial(_scan_records, originals=True) if originals else _scan_records
     need_umi(umi)
     ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim),
-                               ("qc", need_read_qc(qc)), ("dedup", need_dedup(dedup))) if v is not None}
+                               ("qc", need_read_qc(qc)), ("dedup", need_dedup(dedup)),
+                               ("write_reads", write_reads)) if v is not None}
     if ahead or (umi is not None and umi.inline):
         return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
                                    lean=False, **ahead, **({} if umi is None else {"umi": umi}))
@@ -377,17 +413,21 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
                             names: bool = True, originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None, dedup=None,
-                            umi=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None, umi=None,
+                            write_reads=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
     trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
     per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``), ``qc``, ``dedup``: see
-    ``scan_pair_source_stream``.  ``umi``: likewise; "per_read" is "read1" here, and "read2" raises ``ValueError``."""
+    ``scan_pair_source_stream``.  ``umi``: likewise; "per_read" is "read1" here, and "read2" raises ``ValueError``.
+    ``write_reads``: likewise, a ``ReadWriter`` without ``out2``: the reads that still have bases go to ``out1``."""
     from .dedup import need_dedup
     from .read_qc import need_read_qc
     from .umi import need_umi
+    if write_reads is not None:   # (checked first)
+        from .read_write import need_read_writer
+        need_read_writer(write_reads).need_route(("reads",), need_umi(umi))
     need_read_qc(qc)
     need_dedup(dedup)
     if need_umi(umi) is not None:
@@ -400,7 +440,8 @@ def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 
                                **({} if adapter_trim is None else {"adapter_trim": adapter_trim}),
                                **({} if qc is None else {"qc": qc}),
                                **({} if dedup is None else {"dedup": dedup}),
-                               **({} if umi is None else {"umi": umi}))
+                               **({} if umi is None else {"umi": umi}),
+                               **({} if write_reads is None else {"write_reads": write_reads}))
 
 
 def scan_pair_end_text(indexer: Indexer, r1_text: np.ndarray, r2_text: np.ndarray, chunk_bytes: int = 128 << 20,
