@@ -50,30 +50,37 @@ Offered = namedtuple("Offered", "dup totals")
 
 
 class Table:
-    """The set of (key, first, count) a table holds, whatever its layout, and what each call does to it."""
+    """The set of (key, first, count) a table holds, whatever its layout, and what each call does to it.  ``slots``: how
+    many keys the table has room for; None (the default): room for every key.  A key that is not in a table without room
+    is not placed: its record gets no slot, the call counts it in totals [5], and the table stays as it is."""
 
-    def __init__(self):
+    def __init__(self, slots: int = None):
         self.first, self.count = {}, {}
         self.offered = 0
+        self.slots = slots
 
     def insert(self, keys, first_index: int = None):
-        """One ``gf_dd_insert_device`` call: the totals [0], [1], [2] it adds."""
+        """One ``gf_dd_insert_device`` call: the totals [0], [1], [2] and [5] it adds."""
         first_index = self.offered if first_index is None else first_index
-        new = 0
+        new = failed = 0
         for i, k in enumerate(keys):
             if not k:
                 continue
             if k not in self.first:
+                if self.slots is not None and len(self.first) >= self.slots:
+                    failed += 1
+                    continue
                 new += 1
                 self.first[k], self.count[k] = NO_INDEX, 0
             self.first[k] = min(self.first[k], first_index + i)
             self.count[k] += 1
         self.offered = max(self.offered, first_index + len(keys))
-        return [len(keys), sum(1 for k in keys if k), new, 0, 0, 0]
+        return [len(keys), sum(1 for k in keys if k), new, 0, 0, failed]
 
     def duplicates(self, keys, first_index: int):
-        """One ``gf_dd_remove_device`` call behind the insert of the same keys: 1 for every duplicate."""
-        return [int(bool(k) and self.first[k] != first_index + i) for i, k in enumerate(keys)]
+        """One ``gf_dd_remove_device`` call behind the insert of the same keys: 1 for every duplicate; a record whose key
+        found no room has no slot and is none."""
+        return [int(bool(k) and k in self.first and self.first[k] != first_index + i) for i, k in enumerate(keys)]
 
     def offer(self, records, first_index: int = None) -> Offered:
         """Insert, then remove: ``records`` are reads (bytes) or pairs of them.  (duplicate flags, the six totals)."""

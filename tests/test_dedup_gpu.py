@@ -263,6 +263,111 @@ def test_remove_everything_and_nothing(ix):
     assert not any(want.dup) and want.totals == [300, 300, 300, 0, 0, 0]
 
 
+# ---- indices past 32 bits, a table with no room, a rehash without counts ------------------------------------------------
+
+BIG_INDEX = (1 << 40) + 7
+
+
+def _distinct_reads(rng, n, shortest, longest):
+    reads = set()
+    while len(reads) < n:
+        reads.add(bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), int(rng.integers(shortest, longest + 1)))))
+    return sorted(reads)
+
+
+def _offer_at(ix, table, t, reads, first_index, lead=0):
+    """Keys, insert and remove of single-end ``reads`` at ``first_index``, with totals of their own: duplicate flags,
+    totals and the records that leave against the model.  Returns (the model's answer, the records' slots)."""
+    batch, totals = _batch(reads, lead), _totals()
+    rec_keys = dd.keys_device(ix, batch)
+    assert _u64(rec_keys).tolist() == [model.key(r) for r in reads]
+    rec_slot = dd.insert_device(ix, rec_keys, first_index, table, totals)
+    out, dup = dd.remove_device(ix, rec_slot, first_index, table, totals, batch)
+    want = t.offer(reads, first_index)
+    assert dup.cpu().numpy().tolist() == want.dup
+    assert totals.cpu().tolist() == want.totals
+    got, off = _cut(out)
+    assert off[0] == 0
+    assert got == [(b"", b"") if d else (r, _quals(r, k)) for k, (r, d) in enumerate(zip(reads, want.dup))]
+    return want, rec_slot.cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_first_index_past_32_bits(ix):
+    """``first`` is a 64-bit minimum and is compared as one: a batch at 2^40 + 7, then the same keys at 2^40 - 300.  The
+    two indices of a key differ above and below bit 32; every ``first_index`` elsewhere is at most 5000."""
+    rng = np.random.default_rng(12)
+    reads = _distinct_reads(rng, 500, 20, 60)
+    reads = reads + reads[100:200] + [b""]                    # repeats inside the batch, and a record without bases
+    table, t = dd.empty_table(4096, "cuda"), model.Table()
+    want, _ = _offer_at(ix, table, t, reads, BIG_INDEX, lead=3)
+    assert want.totals[:4] == [601, 600, 500, 100] and _entries(table) == t.entries()
+    assert {f for _, f, _ in t.entries()} == {BIG_INDEX + i for i in range(500)}
+    lower = (1 << 40) - 300
+    want, _ = _offer_at(ix, table, t, reads, lower, lead=9)
+    assert want.totals[:4] == [601, 600, 0, 100]              # only the repeats inside the batch: every first is this call's
+    assert _entries(table) == t.entries()
+    assert t.entries() == {(model.key(r), lower + i, 4 if 100 <= i < 200 else 2) for i, r in enumerate(reads[:500])}
+    # a third call above both: every record with bases is a duplicate
+    want, _ = _offer_at(ix, table, t, reads, BIG_INDEX + 5000)
+    assert want.totals[2:4] == [0, 600] and _entries(table) == t.entries()
+
+
+@pytest.mark.gpu
+def test_a_table_with_no_room(ix):
+    """1024 distinct keys fill a table of 1024 slots exactly.  Of a second call's 100 new keys none finds room: no slot,
+    counted in totals [5], never a duplicate, the bytes kept; its 200 old keys are found.  The table changes in the counts
+    of those 200 alone."""
+    slots = 1024
+    rng = np.random.default_rng(13)
+    old = _distinct_reads(rng, slots, 20, 40)
+    new = _distinct_reads(rng, 100, 41, 50)
+    table, t = dd.empty_table(slots, "cuda"), model.Table(slots=slots)
+    want, slot = _offer_at(ix, table, t, old, 0, lead=5)
+    assert want.totals == [slots, slots, slots, 0, 0, 0] and sorted(slot.tolist()) == list(range(slots))
+    before = _entries(table)
+    assert before == t.entries() and len(before) == slots
+    again = [old[int(k)] for k in rng.choice(slots, 200, replace=False)]
+    mixed = [(new + again)[int(k)] for k in rng.permutation(300)]
+    is_new = np.array([len(r) > 40 for r in mixed])
+    want, slot = _offer_at(ix, table, t, mixed, slots, lead=11)
+    assert want.totals == [300, 300, 0, 200, sum(len(r) for r in again), 100]
+    assert (slot[is_new] == -1).all() and (slot[~is_new] >= 0).all() and (slot[~is_new] < slots).all()
+    stored = _u64(table.keys)
+    assert [int(stored[s]) for s in slot[~is_new]] == [model.key(r) for r, n in zip(mixed, is_new) if not n]
+    assert not any(d for d, n in zip(want.dup, is_new) if n) and all(d for d, n in zip(want.dup, is_new) if not n)
+    found = {model.key(r) for r in again}
+    assert _entries(table) == t.entries() == {(k, f, c + (k in found)) for k, f, c in before}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("old_counted,new_counted", [(True, False), (False, True)])
+def test_rehash_between_a_counted_and_an_uncounted_table(ix, old_counted, new_counted):
+    """The set of (key, first) is kept; the side that has no counts is not touched, and the old table stays as it is."""
+    import torch
+    old, totals, t = dd.empty_table(1024, "cuda", old_counted), _totals(), model.Table()
+    keys = [(k << 10) | 1023 for k in range(1, 201)] + _distinct_keys(300, salt=6)
+    _insert(ix, old, keys + keys[:50], 3, totals)
+    t.insert(keys + keys[:50], 3)
+    held = [None if x is None else x.clone() for x in old]
+    new = dd.Table(torch.full((4096,), 77, dtype=torch.int64, device="cuda"),       # (the call empties it)
+                   torch.full((4096,), 77, dtype=torch.int64, device="cuda"),
+                   torch.full((4096,), 77, dtype=torch.int32, device="cuda") if new_counted else None)
+    dd.rehash_device(ix, old, new)
+    assert _entries(new, counted=False) == _entries(old, counted=False) == t.entries(False) and len(t.entries()) == 500
+    for x, x0 in zip(old, held):
+        assert (x is None and x0 is None) or torch.equal(x, x0)
+    if new_counted:   # emptied, and nothing to add from
+        assert not bool(new.count.any())
+    else:
+        assert _entries(old) == t.entries()
+    # later inserts find the old keys
+    again = keys[100:400] + _distinct_keys(40, salt=7)
+    _insert(ix, new, again, 900, totals)
+    added = t.insert(again, 900)
+    assert added[2] == 40 and _entries(new, counted=False) == t.entries(False) and totals.cpu().tolist()[5] == 0
+
+
 # ---- histogram ----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.gpu
