@@ -122,6 +122,9 @@ def parser() -> argparse.ArgumentParser:
                     "per_read cuts off into the names, as :UMI at the end of the first token (needs --out1)")
     wr.add_argument("--out-compression", type=int, default=None, metavar="N", help="zlib's level for .gz outputs, 1 to "
                     "9, default 4 (needs --out1)")
+    wr.add_argument("--out-deflate", choices=("host", "device"), default=None, help="who compresses .gz outputs: host, "
+                    "the host's zlib (the default), or device, BGZF members deflated on the device, which needs every "
+                    "output to end in .gz and takes no --out-compression level (needs --out1)")
     return p
 
 
@@ -193,17 +196,19 @@ def _umi(args):
 
 
 def _read_writer(args):
-    """The ``ReadWriter`` the options ask for, None without ``--out1``; ``ValueError`` for one of the other three
+    """The ``ReadWriter`` the options ask for, None without ``--out1``; ``ValueError`` for one of the other four
     without it, and for a value out of range."""
     if args.out1 is None:
         for option, given in (("--out2", args.out2 is not None), ("--umi-in-name", args.umi_in_name),
-                              ("--out-compression", args.out_compression is not None)):
+                              ("--out-compression", args.out_compression is not None),
+                              ("--out-deflate", args.out_deflate is not None)):
             if given:
                 raise ValueError("%s needs --out1" % option)
         return None
     from .read_write import ReadWriter
     return ReadWriter(args.out1, args.out2, umi_in_name=args.umi_in_name,
-                      **({} if args.out_compression is None else {"compress_level": args.out_compression}))
+                      **({} if args.out_compression is None else {"compress_level": args.out_compression}),
+                      **({} if args.out_deflate is None else {"deflate": args.out_deflate}))
 
 
 def _missing(args) -> Optional[str]:

@@ -141,12 +141,14 @@ def write_totals_counters(totals) -> dict:
 class _FileWriter(threading.Thread):
     """One output file and the thread that writes it, behind a queue of depth 2: the blocks arrive in file order, and
     whoever hands them over waits only when two are already pending.  A name that ends in ``.gz``: every block becomes
-    one gzip member, compressed here; concatenated members are a valid gzip file."""
+    one gzip member, compressed here; concatenated members are a valid gzip file.  ``raw``: the blocks are BGZF members
+    already (deflated on the device) and are written as they are, with ``end`` (the end-of-file marker) behind the last."""
 
-    def __init__(self, path: str, level: int):
+    def __init__(self, path: str, level: int, raw: bool = False, end: bytes = b""):
         super().__init__(name="gf-write-" + os.path.basename(path), daemon=True)
         self.path, self.tmp, self.level = path, path + ".tmp", level
-        self.gz = path.endswith(".gz")
+        self.gz = path.endswith(".gz") and not raw
+        self.end = end
         self.pending: queue.Queue = queue.Queue(maxsize=2)
         self.error: Optional[BaseException] = None
         self.members = 0
@@ -181,6 +183,8 @@ class _FileWriter(threading.Thread):
             try:
                 if self.gz and self.members == 0 and self.error is None:
                     self.f.write(self.member(b""))   # (no record at all: still a gzip file)
+                if self.end and self.error is None:
+                    self.f.write(self.end)
             finally:
                 self.f.close()
 
@@ -193,10 +197,16 @@ class ReadWriter:
     wrote it, the bases and qualities as the steps left them.  ``umi_in_name``: the inline UMI that ``umi`` cuts off
     goes into the name as ``:UMI`` at the end of its first token ("per_read" on pairs: ``:UMI1_UMI2``), the same for
     both mates, so that a later run with ``Umi("name")`` finds it.  ``compress_level``: zlib's, 1 .. 9, for a name that
-    ends in ``.gz``; any other name is written plain.  The files are written as ``name + ".tmp"`` and renamed when the
-    scan ends; a scan that raises leaves neither.  ``ValueError`` for anything else, before a file is opened."""
+    ends in ``.gz``; any other name is written plain.  ``deflate``: who compresses — "host" (the default), the host's
+    zlib, one gzip member a chunk; "device", libgfdeflate.so (``deflate``): the text is deflated where it was formatted,
+    into BGZF members of 65280 bytes of text, and the file ends with the BGZF end-of-file marker, so that bgzip, htslib
+    and a later run with ``inflate="device"`` read it member by member.  "device" needs every output name to end in
+    ``.gz``, and ``compress_level`` is not used with it: the device encoder has one setting.  The files are written as
+    ``name + ".tmp"`` and renamed when the scan ends; a scan that raises leaves neither.  ``ValueError`` for anything
+    else, before a file is opened."""
 
-    def __init__(self, out1: str, out2: Optional[str] = None, umi_in_name: bool = False, compress_level: int = 4):
+    def __init__(self, out1: str, out2: Optional[str] = None, umi_in_name: bool = False, compress_level: int = 4,
+                 deflate: str = "host"):
         for name, v in (("out1", out1),) + ((("out2", out2),) if out2 is not None else ()):
             if not isinstance(v, str) or not v:
                 raise ValueError("ReadWriter.%s must be a file name, not %r" % (name, v))
@@ -204,12 +214,20 @@ class ReadWriter:
             raise ValueError("ReadWriter.umi_in_name must be True or False, not %r" % (umi_in_name,))
         if isinstance(compress_level, bool) or not isinstance(compress_level, int) or not 1 <= compress_level <= 9:
             raise ValueError("ReadWriter.compress_level must be 1 .. 9, not %r" % (compress_level,))
+        if not isinstance(deflate, str) or deflate not in ("host", "device"):
+            raise ValueError("ReadWriter.deflate must be 'host' or 'device', not %r" % (deflate,))
+        if deflate == "device":
+            for v in (out1, out2):
+                if v is not None and not v.endswith(".gz"):
+                    raise ValueError("ReadWriter: deflate='device' writes BGZF, and %r does not end in .gz" % (v,))
         if out2 is not None and _same_file(out1, out2):
             raise ValueError("ReadWriter: out1 and out2 are the same file, %r" % (out1,))
         for v in (out1, out2):
             if v is not None and not os.path.isdir(os.path.dirname(os.path.abspath(v))):
                 raise ValueError("ReadWriter: the directory of %r does not exist" % (v,))
         self.out1, self.out2, self.umi_in_name, self.compress_level = out1, out2, umi_in_name, compress_level
+        self.deflate = deflate
+        self._compressed = None if deflate == "host" else [0] * (1 if out2 is None else 2)
         self._writers = None      # the open files' threads, one per side
         self._free = None         # per side the queue of its two pinned staging blocks (None: not yet allocated)
         self._done = False
@@ -218,6 +236,12 @@ class ReadWriter:
     @property
     def outputs(self) -> tuple:
         return (self.out1,) + (() if self.out2 is None else (self.out2,))
+
+    @property
+    def compressed_bytes(self) -> Optional[tuple]:
+        """Per file the bytes of the members the device deflated (the end-of-file marker not counted); None on the host
+        route, where the writer threads compress."""
+        return None if self._compressed is None else tuple(self._compressed)
 
     def need_route(self, inputs: Sequence[str], umi=None, streamed: bool = True) -> "ReadWriter":
         """``ValueError`` for a route this writer cannot serve: ``inputs`` are the FASTQ files of the scan ((R1, R2) or
@@ -250,8 +274,12 @@ class ReadWriter:
             raise ValueError("write_reads: %d output files for %d sides" % (len(self.outputs), sides))
         self._writers = []
         try:
+            device = {}
+            if self.deflate == "device":
+                from .deflate import EOF_MARKER
+                device = dict(raw=True, end=EOF_MARKER)
             for path in self.outputs:
-                self._writers.append(_FileWriter(path, self.compress_level))
+                self._writers.append(_FileWriter(path, self.compress_level, **device))
             for w in self._writers:
                 w.start()
         except BaseException:
@@ -306,8 +334,14 @@ class ReadWriter:
         takes.  ``pre``: the batches ahead of the UMI cut, used (with ``umi``) only with ``umi_in_name``."""
         tag = dict(pre=[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in pre], umi=umi) \
             if self.umi_in_name else {}
-        return format_reads_device(indexer, texts, cuts,
-                                   [b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in finals], m, **tag)
+        formatted = format_reads_device(indexer, texts, cuts,
+                                        [b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in finals], m, **tag)
+        if self.deflate == "device":
+            # the deflate queued behind the format call, on its output: the text's length stays on the device
+            from .deflate import deflate_device
+            out_texts, out_offs, totals = formatted
+            return formatted + ([deflate_device(text, off[m:m + 1]) for text, off in zip(out_texts, out_offs)],)
+        return formatted
 
     def _staging(self, side: int, nbytes: int):
         """One of the side's two pinned staging blocks, of at least ``nbytes``: waits while both are with the writer."""
@@ -329,14 +363,27 @@ class ReadWriter:
     def collect(self, formatted) -> dict:
         """Behind the chunk's read-back: the totals of ``format_chunk``'s call read, the text of every side copied into
         a staging block and handed to its file's thread.  Returns the chunk's three counters."""
-        out_texts, _, totals = formatted
-        t = [int(x) for x in totals.cpu().tolist()]
+        out_texts, _, totals = formatted[:3]
+        if self.deflate == "device":
+            import torch
+            from .deflate import TOTALS as DEFLATE_TOTALS
+            deflated = formatted[3]
+            both = [int(x) for x in torch.cat([totals] + [d[2] for d in deflated]).cpu().tolist()]   # (one read-back)
+            t = both[:TOTALS]
+            packed = [both[TOTALS + DEFLATE_TOTALS * k:TOTALS + DEFLATE_TOTALS * (k + 1)] for k in range(len(deflated))]
+        else:
+            t = [int(x) for x in totals.cpu().tolist()]
         for side, text in enumerate(out_texts):
             nbytes = t[2 + side]
             if nbytes > text.numel():
                 raise _lib.GfError(_lib.GF_ERR_CAPACITY, "write_reads: a chunk's records are longer than its text")
             if nbytes == 0:
                 continue
+            if self.deflate == "device":   # (the members of this side's text, as they are)
+                text, members, text_bytes, nbytes = deflated[side][0], packed[side][0], packed[side][1], packed[side][2]
+                if text_bytes != t[2 + side] or nbytes > text.numel() or members != -(-text_bytes // 65280):
+                    raise _lib.GfError(_lib.GF_ERR_CAPACITY, "write_reads: the deflate's totals do not fit its text")
+                self._compressed[side] += nbytes
             block = self._staging(side, nbytes)
             block[:nbytes].copy_(text[:nbytes])
             free = self._free[side]
@@ -350,8 +397,9 @@ class ReadWriter:
         return WriteResult(t[0], t[1], (t[2],) + (() if self.out2 is None else (t[3],)), t[4])
 
     def __repr__(self) -> str:
-        return "ReadWriter(out1=%r, out2=%r, umi_in_name=%r, compress_level=%d)" % (
-            self.out1, self.out2, self.umi_in_name, self.compress_level)
+        return "ReadWriter(out1=%r, out2=%r, umi_in_name=%r, compress_level=%d)%s" % (
+            self.out1, self.out2, self.umi_in_name, self.compress_level,
+            "" if self.deflate == "host" else "[deflate=%r]" % (self.deflate,))
 
 
 def _same_file(a: str, b: str) -> bool:
