@@ -20,6 +20,7 @@ from .adapter_trim import AdapterTrim, trim_adapters_device  # noqa: F401
 from .read_qc import ReadQc, QcResult  # noqa: F401
 from .dedup import Dedup, DedupResult  # noqa: F401
 from .umi import Umi  # noqa: F401
+from .overlap_correct import OverlapCorrect, correct_overlaps_device  # noqa: F401
 from .read_write import ReadWriter  # noqa: F401
 
 __version__ = "0.1.0"

@@ -112,6 +112,21 @@ def parser() -> argparse.ArgumentParser:
                     "--umi-loc read1, read2 or per_read)")
     um.add_argument("--umi-skip", type=int, default=None, metavar="N", help="the bases of spacer behind an inline UMI, "
                     "cut off with it, 0 to 32, default 0 (needs --umi-loc)")
+    oc = p.add_argument_group("correction inside the pair overlap (off by default; any of its options switches it on; "
+                              "needs -2)")
+    oc.add_argument("--correct-overlap", action="store_true", help="where the mates of a pair overlap, rewrite a "
+                    "low-quality base that the mate's high-quality base contradicts from the mate, on the device, ahead "
+                    "of the adapter trimming")
+    oc.add_argument("--correct-min-overlap", type=int, default=None, metavar="N", help="the fewest positions an overlap "
+                    "compares, 8 to 512, default 30")
+    oc.add_argument("--correct-max-diff", type=int, default=None, metavar="N", help="the most differences inside an "
+                    "overlap, default 5")
+    oc.add_argument("--correct-diff-percent", type=int, default=None, metavar="N", help="the share of differences "
+                    "inside an overlap, 0 to 100, default 20")
+    oc.add_argument("--correct-good-phred", type=int, default=None, metavar="Q", help="the least phred of the base that "
+                    "is copied, 0 to 93, default 30")
+    oc.add_argument("--correct-bad-phred", type=int, default=None, metavar="Q", help="the most phred of the base that "
+                    "is rewritten, below --correct-good-phred, default 15")
     wr = p.add_argument_group("the cleaned reads as FASTQ files (off by default; --out1 switches them on)")
     wr.add_argument("--out1", default=None, metavar="FILE", help="write the reads (of read1) that are left with bases "
                     "behind the steps above there, formatted on the device; .gz: compressed by the host's zlib.  "
@@ -195,6 +210,24 @@ def _umi(args):
     return Umi(args.umi_loc, **{k: v for k, v in (("length", args.umi_len), ("skip", args.umi_skip)) if v is not None})
 
 
+# option -> the field of ``OverlapCorrect`` it sets
+OVERLAP_CORRECT_OPTIONS = {"correct_min_overlap": "min_overlap", "correct_max_diff": "max_diff",
+                           "correct_diff_percent": "diff_percent", "correct_good_phred": "good_phred",
+                           "correct_bad_phred": "bad_phred"}
+
+
+def _overlap_correct(args):
+    """The ``OverlapCorrect`` the options ask for, None when none of them is given; ``ValueError`` for a value out of
+    range, and without ``-2``: the correction needs pairs."""
+    given = {f: getattr(args, k) for k, f in OVERLAP_CORRECT_OPTIONS.items() if getattr(args, k) is not None}
+    if not (args.correct_overlap or given):
+        return None
+    if not args.read2:
+        raise ValueError("--correct-overlap needs pairs: give read2 with -2")
+    from .overlap_correct import OverlapCorrect
+    return OverlapCorrect(**given)
+
+
 def _read_writer(args):
     """The ``ReadWriter`` the options ask for, None without ``--out1``; ``ValueError`` for one of the other four
     without it, and for a value out of range."""
@@ -253,6 +286,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         umi = _umi(args)
         if umi is not None:
             common["umi"] = umi
+        overlap_correct = _overlap_correct(args)
+        if overlap_correct is not None:
+            common["overlap_correct"] = overlap_correct
         write_reads = _read_writer(args)
         if write_reads is not None:   # (the records are written by the streamed routes)
             common["write_reads"] = write_reads

@@ -159,7 +159,7 @@ def report_names(report_file: str, csv_paths: Sequence[str]) -> List[str]:
 
 def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int] = None, inflate: str = "host",
                       originals: bool = False, *, read_filter=None, adapter_trim=None, qc=None, dedup=None,
-                      umi=None, write_reads=None):
+                      umi=None, write_reads=None, overlap_correct=None):
     """One streamed pass over the FASTQ ``files`` ((R1, R2) or (reads,)) for all ``indexers``: per index what
     ``scan.streamed_found`` gives for it alone — (matches in push order, counters in front of the filter counts, those
     behind them).  The chunk loop is scan_stream's; what is plugged in is the scan of one chunk's records against
@@ -178,8 +178,11 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     ``umi``: a ``Umi``, every chunk's records are tagged once, ahead of the trimming (``scan_stream._scan_chunk``); every
     index reports the same five totals in front of the trimming's.  ``write_reads``: a ``ReadWriter``, every chunk's
     records that are left with bases are written once, whatever the number of indexes; every index reports the same three
-    totals behind the duplicate removal's."""
+    totals behind the duplicate removal's.  ``overlap_correct``: an ``OverlapCorrect``, every chunk's pairs are
+    corrected once, between the UMI step and the trimming (``scan_stream._scan_chunk``); every index reports the same
+    five totals between theirs."""
     from . import scan_pack, scan_stream
+    from .overlap_correct import CORRECT_COUNTER_KEYS
     from .adapter_trim import ADAPTER_COUNTER_KEYS
     from .dedup import DEDUP_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
@@ -193,7 +196,8 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
     mappers = [FusionMapper(ix) for ix in indexers]
     found = [[] for _ in indexers]
     sums = [{count_key: 0, "merged_pairs": 0, "retried_reads": 0} for _ in indexers]
-    extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
+    extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if overlap_correct is None else CORRECT_COUNTER_KEYS) \
+        + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
         + (() if read_filter is None else COUNTER_KEYS) + (() if dedup is None else DEDUP_COUNTER_KEYS)
     if write_reads is not None:
         from .read_write import WRITE_COUNTER_KEYS
@@ -247,7 +251,9 @@ def _stream_multi_csv(indexers, files, chunk_bytes: int, hits_cap: Optional[int]
                                                          **({} if dedup is None else {"dedup": dedup}),
                                                          **({} if umi is None else {"umi": umi}),
                                                          **({} if write_reads is None else
-                                                            {"write_reads": write_reads})):
+                                                            {"write_reads": write_reads}),
+                                                         **({} if overlap_correct is None else
+                                                            {"overlap_correct": overlap_correct})):
             for k, (rec, hb, hq, names, tot, *orig) in enumerate(per_index):
                 found[k] += named_from_device(finish_pair_hits(mappers[k], rec, hb, hq), rec, names, *orig)
                 for key in sums[k]:
@@ -267,7 +273,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                           hits_cap: int = None, inflate: str = "host", tail: str = "host", originals: bool = False,
                           html_file: str = "", *, read_filter=None, adapter_trim=None,
                           qc=None, dedup=None, umi=None,
-                          write_reads=None) -> List[Tuple[str, List[FusionResult], dict]]:
+                          write_reads=None, overlap_correct=None) -> List[Tuple[str, List[FusionResult], dict]]:
     """``scan_per_fusion_csv``: ``[(csv_path, results, counters)]`` in list order, each entry what
     ``scan.scan_pair_end_report`` (or, without ``read2_file``, ``scan.scan_single_end_report``) returns for that CSV
     alone: the whole-file routes of scan.py, piece by piece.  The FASTA is read once and the FASTQ cut once; with
@@ -316,7 +322,12 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
 
     ``write_reads``: None or a ``read_write.ReadWriter``, the cleaned records written out as FASTQ files
     (``scan.scan_pair_end_files``): streamed mode only — ``ValueError`` without ``chunk_bytes`` — and once, however many
-    CSVs; every CSV reports the same three totals."""
+    CSVs; every CSV reports the same three totals.
+
+    ``overlap_correct``: None or an ``overlap_correct.OverlapCorrect``, bases inside the overlap of a pair corrected
+    from the mate between the UMI step and the trimming (``scan.scan_pair_end_files``): once as well — a list of CSVs
+    is corrected once — and every CSV reports the same five totals.  Without ``read2_file`` it raises ``ValueError``:
+    the correction needs pairs."""
     if write_reads is not None:   # (checked first)
         from .read_write import need_read_writer
         need_read_writer(write_reads)
@@ -333,6 +344,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
     need_dedup(dedup)
     if need_umi(umi) is not None:
         umi.need_sides(2 if read2_file else 1)
+    from .overlap_correct import need_pairs
+    need_pairs(overlap_correct, bool(read2_file))
     if write_reads is not None:
         write_reads.need_route((read1_file, read2_file) if read2_file else (read1_file,), umi, chunk_bytes is not None)
     if need_adapter_trim(adapter_trim) is not None and not read2_file and not adapter_trim.adapter_r1:
@@ -369,7 +382,8 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                           **({} if qc is None else {"qc": qc}),
                                           **({} if dedup is None else {"dedup": dedup}),
                                           **({} if umi is None else {"umi": umi}),
-                                          **({} if write_reads is None else {"write_reads": write_reads}))
+                                          **({} if write_reads is None else {"write_reads": write_reads}),
+                                          **({} if overlap_correct is None else {"overlap_correct": overlap_correct}))
                         if opened else [])
             for csv, (ix, fusions), (found, before, after) in zip(csvs, opened, produced):
                 kept, counters = finish_matches(found, FusionMapper(ix), settings.deletion_threshold, False, before, after,
@@ -378,7 +392,7 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
         for k, (_, results, _) in enumerate(out):
             write(k, results)
         return out
-    reads = prepared = counted = trimmed = deduplicated = tagged = None
+    reads = prepared = counted = trimmed = deduplicated = tagged = corrected = None
     for k, csv in enumerate(csvs):
         with open_index(refs[k], csv, device) as (ix, fusions):
             if reads is None:   # (the first index names the device the records go to)
@@ -386,11 +400,15 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                     (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
                     measured_reads(ix, qc, "before", l, r)
                     (l, r), codes, tagged = tagged_reads(ix, umi, ltext, l, r)
+                    if overlap_correct is not None:   # (the helper is called only when the step is asked for)
+                        from .scan import corrected_reads
+                        (l, r), corrected = corrected_reads(ix, overlap_correct, l, r)
                     (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
                     (l, r), counted = filtered_reads(ix, read_filter, l, r)
                     (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r,
                                                               **({} if codes is None else {"umi_codes": codes}))
-                    if adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi):
+                    if (adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi)
+                            or overlap_correct is not None):
                         measured_reads(ix, qc, "after", l, r)
                     reads = (l, ltext), (r, rtext)
                     prepared = prepare_pairs_device(ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets,
@@ -411,7 +429,10 @@ def scan_multi_csv_report(ref_file: str, csv_list_file: str, read1_file: str, re
                                        lambda **caps: scan_prepared_pairs_device(ix, prepared, **caps), originals)
             else:
                 produced = single_end_found(ix, mapper, *reads, originals)
-            produced = deduplicated(counted(trimmed(tagged(produced))))
+            produced = tagged(produced)
+            if corrected is not None:
+                produced = corrected(produced)
+            produced = deduplicated(counted(trimmed(produced)))
             kept, counters = finish_matches(produced[0], mapper, settings.deletion_threshold, False, *produced[1:],
                                             tail=tail)
             results, counters = report_matches(kept, counters, fusions, list(ix.m_fusion_seq), settings, tail, device)
@@ -425,7 +446,7 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
                 chunk_bytes: int = None, ref_chunk_bytes: int = None, inflate: str = "host", tail: str = "host",
                 originals: bool = False, html_file: str = "", route: str = "device", remove_alignables: bool = False, *,
                 alignable_filter: str = None, read_filter=None, adapter_trim=None, qc=None, dedup=None,
-                umi=None, write_reads=None):
+                umi=None, write_reads=None, overlap_correct=None):
     """The mode switch of ``FusionScan::scan`` (fusion_scan.rs:311-330): a fusion file with the extension ``csv`` goes
     to the single-CSV scanners (``scan.scan_pair_end_report`` with ``read2_file``, else
     ``scan.scan_single_end_report``) and gives their ``(results, counters)``; anything else is a list of CSVs and
@@ -448,7 +469,10 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
     ``umi``: None or a ``umi.Umi``, the UMIs cut off or read from the names ahead of the trimming and keyed into ``dedup``,
     in every mode, handed on only when set; a list of CSVs is tagged once.  ``write_reads``: None or a
     ``read_write.ReadWriter``, the cleaned records written out as FASTQ files by the streamed routes, handed on only
-    when set; ``ValueError`` without ``chunk_bytes``."""
+    when set; ``ValueError`` without ``chunk_bytes``.  ``overlap_correct``: None or an
+    ``overlap_correct.OverlapCorrect``, bases inside the overlap of a pair corrected from the mate ahead of the
+    trimming, in every mode with pairs, handed on only when set; ``ValueError`` without ``read2_file``; a list of CSVs
+    is corrected once."""
     from . import scan
     if write_reads is not None:   # (checked first)
         from .read_write import need_read_writer
@@ -468,6 +492,9 @@ def scan_report(ref_file: str, fusion_file: str, read1_file: str, read2_file: st
         filtered["dedup"] = dedup
     if need_umi(umi) is not None:
         filtered["umi"] = umi
+    from .overlap_correct import need_pairs
+    if need_pairs(overlap_correct, bool(read2_file)) is not None:
+        filtered["overlap_correct"] = overlap_correct
     if write_reads is not None:
         write_reads.need_route((read1_file, read2_file) if read2_file else (read1_file,), umi, chunk_bytes is not None)
         filtered["write_reads"] = write_reads

@@ -240,6 +240,11 @@ ADAPTER_CUTTING = (("adapter_trimmed_reads", "adapter_reads_cut"), ("adapter_tri
                    ("overlapping_pairs", "adapter_overlapping_pairs"))
 
 
+OVERLAP_CORRECTION = (("overlapping_pairs", "correction_overlapping_pairs"),
+                      ("pairs_with_differences", "correction_pairs_with_diffs"), ("corrected_reads", "corrected_reads"),
+                      ("corrected_bases", "corrected_bases"), ("differences_left", "correction_diffs_left"))
+
+
 UMI_COUNTS = (("tagged_reads", "umi_reads_tagged"), ("reads_without_umi", "umi_missing"), ("umis_with_N", "umi_with_n"),
               ("cut_bases", "umi_bases_cut"), ("too_short_reads", "umi_too_short"))
 
@@ -252,6 +257,8 @@ def report_document(result: QcResult, counters: Optional[dict] = None, duplicati
         doc["filtering_result"] = {name: int(counters[key]) for name, key in FILTERING_RESULT}
     if counters is not None and "adapter_reads_cut" in counters:
         doc["adapter_cutting"] = {name: int(counters[key]) for name, key in ADAPTER_CUTTING}
+    if counters is not None and "corrected_reads" in counters:
+        doc["overlap_correction"] = {name: int(counters[key]) for name, key in OVERLAP_CORRECTION}
     if counters is not None and "umi_reads_tagged" in counters:
         doc["umi"] = {**({} if umi is None else umi.describe()),
                       **{name: int(counters[key]) for name, key in UMI_COUNTS}}
@@ -270,7 +277,8 @@ def report_document(result: QcResult, counters: Optional[dict] = None, duplicati
 def report_json(result: QcResult, counters: Optional[dict] = None, duplication=None, umi=None) -> str:
     """This project's own QC document, with fastp's key names where the statistic is the same: ``summary`` with
     ``before_filtering`` / ``after_filtering`` (``QcResult.summary``); with ``counters`` of a scan that ran them
-    ``filtering_result`` (the read filter's counts), ``adapter_cutting`` (the trimming's) and ``umi`` (the UMI step's five
+    ``filtering_result`` (the read filter's counts), ``adapter_cutting`` (the trimming's), ``overlap_correction`` (the
+    overlap correction's five counts, behind ``adapter_cutting``) and ``umi`` (the UMI step's five
     counts, and with ``umi``, the scan's ``umi.Umi``, its ``source``, ``length`` and ``skip`` in front); with ``duplication``, a
     ``dedup.DedupResult``, ``duplication``: the ``rate``, duplicates over the records checked (0.0 over 0), and the
     ``histogram``, entry c - 1 the keys offered c times, the last one those offered 31 times or more; ``insert_size``

@@ -191,6 +191,23 @@ def trimmed_reads(ix: Indexer, adapter_trim, *batches):
     return tuple(kept), counted
 
 
+def corrected_reads(ix: Indexer, overlap_correct, *batches):
+    """The ``FastqBatch``es of a pair through the overlap correction on the index's device (overlap_correct.py), behind
+    ``tagged_reads`` and ahead of ``trimmed_reads``, which needs both mates uncut: (the batches it leaves,
+    ``counted(produced)``).  ``counted`` adds the correction's five totals to the end of a producer's counters in front
+    of the filter counts — so it is applied before ``trimmed_reads``' — and ``overlap_correct`` None gives the batches
+    as they are, nothing queued, and a ``counted`` that changes nothing."""
+    if overlap_correct is None:
+        return batches, lambda produced: produced
+    from .overlap_correct import correct_overlaps_device, correct_totals_counters
+    *kept, totals = correct_overlaps_device(ix, overlap_correct, *batches)
+
+    def counted(produced):
+        found, before, after = produced
+        return found, {**before, **correct_totals_counters(totals.cpu().tolist())}, after
+    return tuple(kept), counted
+
+
 def measured_reads(ix: Indexer, qc, stage: str, *batches) -> None:
     """The ``FastqBatch``es added to the tables of ``qc`` (a ``read_qc.ReadQc``) for ``stage``, "before" or "after",
     on the index's device; at "before" the insert lengths of a pair too.  ``qc`` None: nothing is queued."""
@@ -285,7 +302,7 @@ def _single_end_host_found(mapper: FusionMapper, b, text: bytes,
 def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, inflate: str = "host",
                    originals: bool = False, *, read_filter=None,
                    adapter_trim=None, qc=None, dedup=None, umi=None,
-                   write_reads=None) -> Tuple[List[ReadMatch], dict, dict]:
+                   write_reads=None, overlap_correct=None) -> Tuple[List[ReadMatch], dict, dict]:
     """The matches of the FASTQ files ``files`` ((R1, R2) or (reads,)) streamed in chunks (scan_stream.py), in push
     order, each named from its chunk's device-gathered names, and their counters.  ``inflate``: see ``open_index``.
     ``originals``: the matches' FASTQ records are gathered on the device too (``hit_names.hit_records_device``).
@@ -298,8 +315,10 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     the read filter's.  ``umi``: a ``Umi``, every chunk's records go through the UMI step ahead of the adapter
     trimming, and its five totals stand in front of the trimming's.  ``write_reads``: a ``ReadWriter``, every chunk's
     records that are left with bases are written to its files, and its three totals stand behind the duplicate
-    removal's."""
+    removal's.  ``overlap_correct``: an ``OverlapCorrect``, every chunk's pairs go through the overlap correction
+    between the UMI step and the trimming, and its five totals stand between theirs."""
     from .adapter_trim import ADAPTER_COUNTER_KEYS
+    from .overlap_correct import CORRECT_COUNTER_KEYS
     from .dedup import DEDUP_COUNTER_KEYS
     from .read_filter import COUNTER_KEYS
     from .scan_stream import open_fastq_sources, scan_pair_source_stream, scan_single_text_stream
@@ -308,7 +327,8 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     stream = scan_pair_source_stream if len(files) == 2 else scan_single_text_stream
     found: List[ReadMatch] = []
     sums = {count_key: 0, "merged_pairs": 0, "retried_reads": 0}
-    extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
+    extra = (() if umi is None else UMI_COUNTER_KEYS) + (() if overlap_correct is None else CORRECT_COUNTER_KEYS) \
+        + (() if adapter_trim is None else ADAPTER_COUNTER_KEYS) \
         + (() if read_filter is None else COUNTER_KEYS) + (() if dedup is None else DEDUP_COUNTER_KEYS)
     if write_reads is not None:
         from .read_write import WRITE_COUNTER_KEYS
@@ -317,8 +337,8 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
     chunks = 0
     with ExitStack() as opened:
         sources = open_fastq_sources(opened, files, inflate)
-        # (originals=False, read_filter=None, adapter_trim=None, qc=None, dedup=None, umi=None and write_reads=None are
-        #  not passed on: the stream is then called as it always was)
+        # (originals=False, read_filter=None, adapter_trim=None, qc=None, dedup=None, umi=None, write_reads=None and
+        #  overlap_correct=None are not passed on: the stream is then called as it always was)
         for rec, hb, hq, names, tot, *orig in stream(ix, *sources, chunk_bytes, max_read_len=None,
                                                      **({"originals": True} if originals else {}),
                                                      **({"read_filter": read_filter} if read_filter is not None else {}),
@@ -327,7 +347,8 @@ def streamed_found(ix: Indexer, mapper: FusionMapper, files, chunk_bytes: int, i
                                                      **({"dedup": dedup} if dedup is not None else {}),
                                                      **({"umi": umi} if umi is not None else {}),
                                                      **({"write_reads": write_reads} if write_reads is not None
-                                                        else {})):
+                                                        else {}),
+                                                     **({"overlap_correct": overlap_correct} if overlap_correct is not None else {})):
             found += named_from_device(finish_pair_hits(mapper, rec, hb, hq), rec, names, *orig)
             for k in sums:
                 sums[k] += tot[k]
@@ -362,7 +383,7 @@ def _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes) ->
 def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold, remove_alignables,
                       chunk_bytes, ref_chunk_bytes=None, inflate="host", tail="host", originals=False,
                       alignable_filter=None, read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None,
-                      write_reads=None):
+                      write_reads=None, overlap_correct=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_pair_end_files`` and what the report needs."""
     if write_reads is not None:   # (checked first)
         from .read_write import need_read_writer
@@ -379,6 +400,8 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
     need_read_qc(qc)
     need_dedup(dedup)
     need_umi(umi)
+    from .overlap_correct import need_overlap_correct
+    need_overlap_correct(overlap_correct)
     if write_reads is not None:
         write_reads.need_route((read1_file, read2_file), umi, chunk_bytes is not None)
     _need_whole_contigs(alignable_filter, remove_alignables, ref_chunk_bytes)
@@ -395,22 +418,30 @@ def _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, dele
                                       **({"qc": qc} if qc is not None else {}),
                                       **({"dedup": dedup} if dedup is not None else {}),
                                       **({"umi": umi} if umi is not None else {}),
-                                      **({"write_reads": write_reads} if write_reads is not None else {}))
+                                      **({"write_reads": write_reads} if write_reads is not None else {}),
+                                      **({"overlap_correct": overlap_correct} if overlap_correct is not None else {}))
         else:
             (l, ltext), (r, rtext) = FastqReaderPair.from_paths(read1_file, read2_file).read_all_device(ix)
             measured_reads(ix, qc, "before", l, r)
             (l, r), codes, tagged = tagged_reads(ix, umi, ltext, l, r)
+            corrected = None   # (the helper is called only when the step is asked for)
+            if overlap_correct is not None:
+                (l, r), corrected = corrected_reads(ix, overlap_correct, l, r)
             (l, r), trimmed = trimmed_reads(ix, adapter_trim, l, r)
             (l, r), counted = filtered_reads(ix, read_filter, l, r)
             (l, r), deduplicated = deduplicated_reads(ix, dedup, l, r, **({} if codes is None else {"umi_codes": codes}))
-            if adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi):
+            if (adapter_trim is not None or read_filter is not None or dedup is not None or _cuts(umi)
+                    or overlap_correct is not None):
                 measured_reads(ix, qc, "after", l, r)
             reads = (l, ltext), (r, rtext)
             max_len = max(l.max_read_len(), r.max_read_len(), 1)
             # the records never leave HBM between the FASTQ cut and the hit list: one device call for the pack
-            produced = deduplicated(counted(trimmed(tagged(pairs_found(
+            produced = tagged(pairs_found(
                 mapper, reads, max_len, lambda **caps: scan_pairs_device(
-                    ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals)))))
+                    ix, l.bases, l.quals, l.offsets, r.bases, r.quals, r.offsets, max_len, **caps), originals))
+            if corrected is not None:
+                produced = corrected(produced)
+            produced = deduplicated(counted(trimmed(produced)))
         kept, counters = finish_matches(produced[0], mapper, deletion_threshold, remove_alignables, *produced[1:],
                                         tail=tail, alignable_filter=alignable_filter)
         return kept, counters, fusions, list(ix.m_fusion_seq)
@@ -422,7 +453,8 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
                         inflate: str = "host", tail: str = "host",
                         originals: bool = False, *, alignable_filter: str = None,
                         read_filter=None, adapter_trim=None, qc=None,
-                        dedup=None, umi=None, write_reads=None) -> Tuple[List[ReadMatch], dict]:
+                        dedup=None, umi=None, write_reads=None,
+                        overlap_correct=None) -> Tuple[List[ReadMatch], dict]:
     """Returns (matches kept, in ``sort_matches`` order; counters).  Each match carries the name
     of the read it was found on (``match_named``).
 
@@ -512,13 +544,26 @@ def scan_pair_end_files(ref_file: str, fusion_csv: str, read1_file: str, read2_f
     ``chunk_bytes``, for an output that is an input, and for ``umi_in_name`` without an inline ``umi``.  Alone it
     rewrites the pairs whose mates both have bases.  The counters gain ``written_records``, ``written_bases`` and
     ``written_bytes`` behind the duplicate removal's keys; matches and the other counters are those of the scan
-    without it.  Without it nothing more is queued or allocated."""
+    without it.  Without it nothing more is queued or allocated.
+
+    ``overlap_correct``: None (the default), or an ``overlap_correct.OverlapCorrect``: bases inside the overlap of a
+    pair are corrected from the mate on the device (overlap_correct.py), behind the UMI step and ahead of the adapter
+    trimming, which needs both mates uncut.  The overlap is found as the trimming finds it, the largest accepted insert
+    length; at a difference inside it a base of ``bad_phred`` or less takes the complement and the quality of the
+    mate's base of ``good_phred`` or more, and every other difference is left standing.  The trimming, the read filter,
+    the duplicate removal, ``qc``'s "after" stage, ``write_reads`` and the scan then see corrected records: a pair
+    that three low-quality miscalls kept from merging merges, and PCR copies that differ by such a miscall are
+    duplicates.  Lengths and record indices stay, so names and ``m_original_reads`` are those of the sequencer.  The
+    counters gain ``correction_overlapping_pairs``, ``correction_pairs_with_diffs``, ``corrected_reads``,
+    ``corrected_bases`` and ``correction_diffs_left`` between the UMI step's keys and the trimming's, the same on every
+    route.  ``ValueError`` for anything else.  Without it nothing more is loaded, queued or allocated."""
     return _pair_end_matches(ref_file, fusion_csv, read1_file, read2_file, device, deletion_threshold,
                              remove_alignables, chunk_bytes, ref_chunk_bytes, inflate, tail, originals,
                              alignable_filter, read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
                              **({"dedup": dedup} if dedup is not None else {}),
                              **({"umi": umi} if umi is not None else {}),
-                             **({"write_reads": write_reads} if write_reads is not None else {}))[:2]
+                             **({"write_reads": write_reads} if write_reads is not None else {}),
+                             **({"overlap_correct": overlap_correct} if overlap_correct is not None else {}))[:2]
 
 
 def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_file: str, device: int = -1,
@@ -527,7 +572,7 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                          remove_alignables: bool = False, *,
                          alignable_filter: str = None, read_filter=None,
                          adapter_trim=None, qc=None, dedup=None, umi=None,
-                         write_reads=None) -> Tuple[List[FusionResult], dict]:
+                         write_reads=None, overlap_correct=None) -> Tuple[List[FusionResult], dict]:
     """The whole of ``PairEndScanner::scan`` up to the reporters (pescanner.rs:78-176, :335-337):
     files -> matches -> filter -> per-gene-pair sort -> cluster -> qualified fusions, most
     supported first.  ``report_text`` / ``report_json`` / ``report_html`` of fusion_result.py turn the list into
@@ -536,7 +581,8 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
     filter as it is), ``alignable_filter`` (a last filter that works), ``read_filter`` (a quality filter ahead of the
     scan), ``adapter_trim`` (adapter trimming ahead of that), ``qc`` (the reads measured before and behind the two),
     ``dedup`` (duplicate pairs removed behind the read filter), ``umi`` (UMIs cut off ahead of the trimming and keyed
-    into ``dedup``), ``write_reads`` (the cleaned pairs written out as FASTQ files, streamed routes only): see
+    into ``dedup``), ``write_reads`` (the cleaned pairs written out as FASTQ files, streamed routes only),
+    ``overlap_correct`` (bases inside the pair overlap corrected from the mate, ahead of the trimming): see
     ``scan_pair_end_files``.  ``tail``: "device" also
     clusters in bulk — the first fit of all groups in one host call, the refined breaks of all matches in one
     ``gf_rp_adjust_device`` call (report_tail.py); the same results, counters and report bytes."""
@@ -547,13 +593,15 @@ def scan_pair_end_report(ref_file: str, fusion_csv: str, read1_file: str, read2_
                                              read_filter, adapter_trim, **({"qc": qc} if qc is not None else {}),
                                              **({"dedup": dedup} if dedup is not None else {}),
                                              **({"umi": umi} if umi is not None else {}),
-                                             **({"write_reads": write_reads} if write_reads is not None else {})),
+                                             **({"write_reads": write_reads} if write_reads is not None else {}),
+                                             **({"overlap_correct": overlap_correct} if overlap_correct is not None else {})),
                           settings, tail, device)
 
 
 def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                         ref_chunk_bytes=None, inflate="host", tail="host", originals=False, alignable_filter=None,
-                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None, write_reads=None):
+                        read_filter=None, adapter_trim=None, *, qc=None, dedup=None, umi=None, write_reads=None,
+                        overlap_correct=None):
     """(matches kept, counters, fusions, fusion sequences): ``scan_single_end_files`` and what the report needs."""
     if write_reads is not None:   # (checked first)
         from .read_write import need_read_writer
@@ -570,6 +618,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
     need_dedup(dedup)
     if need_umi(umi) is not None:
         umi.need_sides(1)
+    from .overlap_correct import need_pairs
+    need_pairs(overlap_correct, False)
     if write_reads is not None:
         write_reads.need_route((read1_file,), umi, chunk_bytes is not None)
     if need_adapter_trim(adapter_trim) is not None and not adapter_trim.adapter_r1:
@@ -589,7 +639,8 @@ def _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_thres
                                       **({"qc": qc} if qc is not None else {}),
                                       **({"dedup": dedup} if dedup is not None else {}),
                                       **({"umi": umi} if umi is not None else {}),
-                                      **({"write_reads": write_reads} if write_reads is not None else {}))
+                                      **({"write_reads": write_reads} if write_reads is not None else {}),
+                                      **({"overlap_correct": overlap_correct} if overlap_correct is not None else {}))
         else:   # (both routes start from the records in HBM, where the read filter runs)
             b, text = FastqReader(read1_file).read_all_device(ix)
             measured_reads(ix, qc, "before", b)
@@ -614,7 +665,8 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
                           inflate: str = "host", tail: str = "host",
                           originals: bool = False, *, alignable_filter: str = None,
                           read_filter=None, adapter_trim=None, qc=None,
-                          dedup=None, umi=None, write_reads=None) -> Tuple[List[ReadMatch], dict]:
+                          dedup=None, umi=None, write_reads=None,
+                          overlap_correct=None) -> Tuple[List[ReadMatch], dict]:
     """``SingleEndScanner`` (src/core/sescanner.rs:62-195) up to the sorted, filtered match list:
     every read is mapped, then its reverse complement when it was mapable without a match.
 
@@ -639,13 +691,15 @@ def scan_single_end_files(ref_file: str, fusion_csv: str, read1_file: str, devic
     which is the same here) or read from their names ("name") ahead of the trimming and keyed into ``dedup``, on either
     route; ``ValueError`` for "read2"; see ``scan_pair_end_files``.  ``write_reads``: None or a ``ReadWriter`` without
     ``out2``, the reads that still have bases written to ``out1``, with ``chunk_bytes`` only; see
-    ``scan_pair_end_files``."""
+    ``scan_pair_end_files``.  ``overlap_correct``: anything but None raises ``ValueError``, an ``OverlapCorrect`` too:
+    the correction needs pairs."""
     return _single_end_matches(ref_file, fusion_csv, read1_file, device, deletion_threshold, route, chunk_bytes,
                                ref_chunk_bytes, inflate, tail, originals, alignable_filter, read_filter,
                                adapter_trim, **({"qc": qc} if qc is not None else {}),
                                **({"dedup": dedup} if dedup is not None else {}),
                                **({"umi": umi} if umi is not None else {}),
-                               **({"write_reads": write_reads} if write_reads is not None else {}))[:2]
+                               **({"write_reads": write_reads} if write_reads is not None else {}),
+                             **({"overlap_correct": overlap_correct} if overlap_correct is not None else {}))[:2]
 
 
 def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, device: int = -1,
@@ -654,10 +708,10 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                            tail: str = "host", originals: bool = False, *,
                            alignable_filter: str = None, read_filter=None,
                            adapter_trim=None, qc=None, dedup=None, umi=None,
-                           write_reads=None) -> Tuple[List[FusionResult], dict]:
+                           write_reads=None, overlap_correct=None) -> Tuple[List[FusionResult], dict]:
     """``SingleEndScanner::scan`` up to the reporters: files -> qualified fusions.  ``route``, ``chunk_bytes``,
     ``ref_chunk_bytes``, ``inflate``, ``originals``, ``alignable_filter``, ``read_filter``, ``adapter_trim``, ``qc``, ``dedup``,
-    ``umi``, ``write_reads``: see
+    ``umi``, ``write_reads``, ``overlap_correct``: see
     ``scan_single_end_files``; ``tail``: see
     ``scan_pair_end_report``."""
     settings = settings or Settings()
@@ -667,5 +721,6 @@ def scan_single_end_report(ref_file: str, fusion_csv: str, read1_file: str, devi
                                                **({"qc": qc} if qc is not None else {}),
                                                **({"dedup": dedup} if dedup is not None else {}),
                                                **({"umi": umi} if umi is not None else {}),
-                                               **({"write_reads": write_reads} if write_reads is not None else {})),
+                                               **({"write_reads": write_reads} if write_reads is not None else {}),
+                                             **({"overlap_correct": overlap_correct} if overlap_correct is not None else {})),
                           settings, tail, device)

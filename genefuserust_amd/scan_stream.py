@@ -6,6 +6,7 @@ list happens on the device, chunk k+1 being read and crossing the link while chu
     byte source (a file, gunzipped as it is read; a text in memory)  --readinto, upload threads-->  pinned staging
     block  --H2D, copy stream-->  device text buffer (behind the carried-over tail of the previous chunk)  -->
     gf_fastq_index_device / gf_fastq_gather_device  -->  (on request gf_um_cut_device or gf_um_names_device, the UMIs,
+    gf_oc_correct_device, the correction inside the pair overlap,
     gf_at_trim_device, the adapter trimming, and
     gf_pp_filter_device, the read filter, and the gf_dd_* calls, the duplicate removal, and gf_rw_format_device, the
     cleaned records as FASTQ text for the output files)  -->
@@ -176,6 +177,17 @@ def _trim_chunk(indexer: Indexer, adapter_trim, batches, m: int):
     return kept, totals
 
 
+def _correct_chunk(indexer: Indexer, overlap_correct, batches, m: int):
+    """The first ``m`` pairs through the overlap correction (overlap_correct.py), queued behind ``_umi_chunk`` and ahead
+    of ``_trim_chunk``, which needs both mates uncut: (the batches it leaves, of ``m`` records each, corrected clones of
+    the bases and qualities; its totals, on the device).  The pairs behind them are carried to the next chunk and
+    corrected there, once."""
+    from .overlap_correct import correct_overlaps_device
+    *kept, totals = correct_overlaps_device(indexer, overlap_correct,
+                                            *[b._replace(offsets=b.offsets[:m + 1], n_records=m) for b in batches])
+    return kept, totals
+
+
 def _dedup_chunk(indexer: Indexer, dedup, batches, m: int, umi_codes=None):
     """The first ``m`` records of every side through the duplicate removal (dedup.py), queued behind ``_filter_chunk``:
     (the batches it leaves, of ``m`` records each; its totals, on the device).  Only these ``m`` are offered to the
@@ -208,7 +220,7 @@ def _measure_chunk(indexer: Indexer, qc, stage: str, batches, m: int) -> None:
 
 def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_len: Optional[int], names: bool,
                 scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None, adapter_trim=None,
-                qc=None, dedup=None, umi=None, write_reads=None):
+                qc=None, dedup=None, umi=None, write_reads=None, overlap_correct=None):
     """One chunk for ``ChunkStream.run``: the texts cut into records, the records all sides share scanned by
     ``scan_records``.  The result is (what the stream yields for the chunk or None, records scanned, whether the scan
     ends here).  ``lean``: whether the cut leaves the qualities in the text (default: pairs do).  ``read_filter``: a
@@ -228,12 +240,15 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     (read_write.py) behind ``qc``'s "after" stage and ahead of the scan — the full cut again, for the names the chunk's
     texts and the cut's newline index, for ``umi_in_name`` the batches ahead of the UMI cut — and behind the chunk's
     read-back the text goes to the files' threads; its totals go under ``read_write.WRITE_COUNTER_KEYS``, behind the
-    duplicate removal's.  The records carried over are written with the next chunk, once."""
+    duplicate removal's.  The records carried over are written with the next chunk, once.  ``overlap_correct``: an
+    ``OverlapCorrect``, the overlap correction (``_correct_chunk``) between the UMI step and the trimming — pairs only,
+    the full cut again, and a step for ``qc``'s "after" stage; its totals go under
+    ``overlap_correct.CORRECT_COUNTER_KEYS``, between the UMI step's and the trimming's."""
     from .fastq import fastq_cut_device
     umi_cuts = umi is not None and umi.inline
     if read_filter is not None or adapter_trim is not None or qc is not None or dedup is not None or umi_cuts:
         lean = False
-    if write_reads is not None:
+    if write_reads is not None or overlap_correct is not None:
         lean = False
     # (pairs, lean: the qualities stay in the chunk's text, which lives in the slot's buffer until the scan below is
     #  done; single-end: gf_se_scan_device takes the qualities at the bases' offsets, so the full cut)
@@ -243,11 +258,14 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
     if qc is not None and m > 0:
         _measure_chunk(indexer, qc, "before", batches, m)
     if (read_filter is not None or adapter_trim is not None or dedup is not None or umi is not None
-            or write_reads is not None) and m > 0:
+            or write_reads is not None or overlap_correct is not None) and m > 0:
         kept, counted = batches, {}
         if umi is not None:
             from .umi import umi_totals_counters
             kept, umi_codes, umi_totals = _umi_chunk(indexer, umi, texts, kept, m)
+        if overlap_correct is not None:
+            from .overlap_correct import correct_totals_counters
+            kept, correct_totals = _correct_chunk(indexer, overlap_correct, kept, m)
         if adapter_trim is not None:
             from .adapter_trim import adapter_totals_counters
             kept, trim_totals = _trim_chunk(indexer, adapter_trim, kept, m)
@@ -259,7 +277,8 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
             kept, dedup_totals = _dedup_chunk(indexer, dedup, kept, m,
                                               **({} if umi is None else {"umi_codes": umi_codes}))
         # (the name source moves no byte: alone it leaves nothing to measure "after", as on the whole-file routes)
-        if qc is not None and (read_filter is not None or adapter_trim is not None or dedup is not None or umi_cuts):
+        if qc is not None and (read_filter is not None or adapter_trim is not None or dedup is not None or umi_cuts
+                               or overlap_correct is not None):
             _measure_chunk(indexer, qc, "after", kept, m)
         if write_reads is not None:
             formatted = write_reads.format_chunk(indexer, texts, batches, kept, m,
@@ -267,6 +286,8 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
         out = scan_records(indexer, texts, kept, m, done, max_read_len, names)
         if umi is not None:
             counted.update(umi_totals_counters(umi_totals.cpu().tolist()))
+        if overlap_correct is not None:
+            counted.update(correct_totals_counters(correct_totals.cpu().tolist()))
         if adapter_trim is not None:
             counted.update(adapter_totals_counters(trim_totals.cpu().tolist()))
         if read_filter is not None:
@@ -288,16 +309,18 @@ def _scan_chunk(indexer: Indexer, side_names, texts, final, done: int, max_read_
 
 def _scan_source_stream(indexer: Indexer, sources, chunk_bytes: int, max_read_len: Optional[int], names: bool,
                         scan_records=_scan_records, lean: Optional[bool] = None, *, read_filter=None,
-                        adapter_trim=None, qc=None, dedup=None, umi=None, write_reads=None):
+                        adapter_trim=None, qc=None, dedup=None, umi=None, write_reads=None, overlap_correct=None):
     """The chunk loop of both layouts: ``sources`` is (R1, R2) or (reads,).  Yields per chunk what ``scan_records`` gives
     for it — by default (records, hit bases, hit qualities, names or None, totals); ``multi_csv_scan`` plugs in the scan
     of one chunk against K indexes, with ``lean=False`` (``_scan_chunk``).  ``read_filter``: a ``ReadFilter``, handed
     to ``_scan_chunk`` (only when set); ``adapter_trim``: an ``AdapterTrim``, likewise; ``qc``: a ``ReadQc``, likewise;
     ``dedup``: a ``Dedup``, likewise; ``umi``: a ``Umi``, likewise.  ``write_reads``: a ``ReadWriter``, likewise; its
     files are opened before the first chunk, renamed to their names when the stream ends, and removed when it raises or
-    is closed early."""
+    is closed early.  ``overlap_correct``: an ``OverlapCorrect``, likewise."""
     import torch
     filtered = {} if read_filter is None else {"read_filter": read_filter}
+    if overlap_correct is not None:
+        filtered["overlap_correct"] = overlap_correct
     if adapter_trim is not None:
         filtered["adapter_trim"] = adapter_trim
     if qc is not None:
@@ -350,8 +373,8 @@ def open_fastq_sources(opened, files, inflate: str = "host") -> list:
 def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes: int = 128 << 20,
                             max_read_len: Optional[int] = 320, names: bool = True,
                             originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None, dedup=None, umi=None,
-                            write_reads=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None, umi=None, write_reads=None,
+                            overlap_correct=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The paired-end scan of two byte sources of FASTQ text — anything with ``readinto(memoryview) -> int`` (0 at
     the end): ``ArraySource``, ``fastq.FastqReader.open_stream()``; or a ``bgzf.BgzfSource`` — chunk by chunk.  Yields,
     per chunk, (gf_pair_hit records with pair ids counted from the start of the files, the matched reads' bases, their qualities, the names of
@@ -381,10 +404,18 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     thread each; the chunk's totals gain its three counts (``read_write.WRITE_COUNTER_KEYS``) behind the duplicate
     removal's.  A chunk writes the pairs it scans, never the ones it carries over; the files get their names when the
     stream ends and are removed when it raises.  Alone it rewrites the pairs whose mates both have bases.  None (the
-    default): nothing more is queued.  ``ValueError`` for anything else."""
+    default): nothing more is queued.  ``overlap_correct``: an ``overlap_correct.OverlapCorrect``, every chunk's pairs go
+    through the overlap correction between the UMI step and the trimming — the full cut again: inside the overlap of
+    the mates a poor base that the mate's good base contradicts is rewritten from it, so that the trimming, the filter,
+    the removal, ``qc``'s "after" stage, ``write_reads`` and the scan see corrected records; the chunk's totals gain its
+    five counts (``overlap_correct.CORRECT_COUNTER_KEYS``) between the UMI step's and the trimming's.  A chunk corrects
+    the pairs it scans, never the ones it carries over.  None (the default): nothing more is queued.  ``ValueError``
+    for anything else."""
     from .dedup import need_dedup
+    from .overlap_correct import need_overlap_correct
     from .read_qc import need_read_qc
     from .umi import need_umi
+    need_overlap_correct(overlap_correct)
     if write_reads is not None:   # (checked first)
         from .read_write import need_read_writer
         need_read_writer(write_reads).need_route(("R1", "R2"), need_umi(umi))
@@ -392,7 +423,7 @@ def scan_pair_source_stream(indexer: Indexer, r1_source, r2_source, chunk_bytes:
     need_umi(umi)
     ahead = {k: v for k, v in (("read_filter", read_filter), ("adapter_trim", adapter_trim),
                                ("qc", need_read_qc(qc)), ("dedup", need_dedup(dedup)),
-                               ("write_reads", write_reads)) if v is not None}
+                               ("write_reads", write_reads), ("overlap_correct", overlap_correct)) if v is not None}
     if ahead or (umi is not None and umi.inline):
         return _scan_source_stream(indexer, (r1_source, r2_source), chunk_bytes, max_read_len, names, scan_records,
                                    lean=False, **ahead, **({} if umi is None else {"umi": umi}))
@@ -413,18 +444,21 @@ def scan_pair_text_stream(indexer: Indexer, r1_text: np.ndarray, r2_text: np.nda
 
 def scan_single_text_stream(indexer: Indexer, source, chunk_bytes: int = 128 << 20, max_read_len: Optional[int] = 320,
                             names: bool = True, originals: bool = False, *, read_filter=None, adapter_trim=None,
-                            qc=None, dedup=None, umi=None,
-                            write_reads=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
+                            qc=None, dedup=None, umi=None, write_reads=None,
+                            overlap_correct=None) -> Iterator[Tuple[np.ndarray, bytes, bytes, Optional[List[bytes]], dict]]:
     """The single-end counterpart: one byte source (a uint8 array is wrapped into an ``ArraySource``), scanned chunk by
     chunk with ``single_end.scan_single_device`` (``read_id_base`` = reads done so far).  Yields per chunk (records, hit
     bases, hit qualities, names, totals); ``totals["reads"]`` is the chunk's record count.  A final record without a
     trailing newline counts (fastq_reader.rs:75-147).  ``originals``: see ``scan_pair_source_stream``; one FASTQ record
     per hit record.  ``read_filter``, ``adapter_trim`` (which needs ``adapter_r1``), ``qc``, ``dedup``: see
     ``scan_pair_source_stream``.  ``umi``: likewise; "per_read" is "read1" here, and "read2" raises ``ValueError``.
-    ``write_reads``: likewise, a ``ReadWriter`` without ``out2``: the reads that still have bases go to ``out1``."""
+    ``write_reads``: likewise, a ``ReadWriter`` without ``out2``: the reads that still have bases go to ``out1``.
+    ``overlap_correct``: anything but None raises ``ValueError``, an ``OverlapCorrect`` too: the correction needs pairs."""
     from .dedup import need_dedup
+    from .overlap_correct import need_pairs
     from .read_qc import need_read_qc
     from .umi import need_umi
+    need_pairs(overlap_correct, False)
     if write_reads is not None:   # (checked first)
         from .read_write import need_read_writer
         need_read_writer(write_reads).need_route(("reads",), need_umi(umi))

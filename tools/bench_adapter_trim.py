@@ -26,8 +26,9 @@ L = 150
 TRUSEQ = (b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT")
 
 
-def make_reads(genes, n, seed, dev):
-    """(R1 bases, R2 bases) as (n, L) uint8 tensors, and the fragment lengths."""
+def make_reads(genes, n, seed, dev, with_flips=False):
+    """(R1 bases, R2 bases) as (n, L) uint8 tensors, and the fragment lengths; ``with_flips``: and, per mate, the (n, L)
+    mask of the bases that were flipped."""
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
     G = torch.from_numpy(np.frombuffer(b"".join(genes.seqs), dtype=np.uint8).copy()).to(dev)
@@ -39,7 +40,7 @@ def make_reads(genes, n, seed, dev):
     start = (torch.rand(n, device=dev, generator=gen) * (G.numel() - 401)).to(torch.int64)
     flip = torch.rand(n, device=dev, generator=gen) < 0.5      # the fragment's strand
     j = torch.arange(L, device=dev, dtype=torch.int64)[None, :]
-    out = []
+    out, flips = [], []
     for mate in (0, 1):
         # mate 0 reads the fragment from its start, mate 1 the other strand from its end; on the flipped strand they swap
         forward = flip if mate else ~flip
@@ -55,7 +56,8 @@ def make_reads(genes, n, seed, dev):
         wrong = torch.rand((n, L), device=dev, generator=gen) < 1 / 200
         other = acgt[torch.randint(0, 4, (n, L), device=dev, generator=gen)]
         out.append(torch.where(wrong & (other != reads), other, reads).contiguous())
-    return out[0], out[1], F
+        flips.append(wrong & (other != reads))
+    return (out[0], out[1], F, flips) if with_flips else (out[0], out[1], F)
 
 
 def main():
