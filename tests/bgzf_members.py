@@ -1,6 +1,7 @@
 """BGZF members for the tests of the device inflate: members made by zlib in every block kind, members assembled bit by
 bit that zlib cannot emit but must accept, malformed members, and ``walk_model``, a restatement of gf_if_walk_blocks
-(include/gf_inflate.h) in Python.  The expected text comes from zlib / gzip everywhere."""
+(include/gf_inflate.h) in Python.  The expected text comes from zlib / gzip everywhere.  ``deep_codes``: members at the
+limits of the code lengths; ``tokens_of``: a dynamic block taken apart into its code lengths and tokens."""
 import struct
 import zlib
 
@@ -192,10 +193,15 @@ _CL_SYMS = list(range(13)) + [16, 17, 18]
 _CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
 
 
-def dynamic_header(items, nlen: int, ndist: int, cl_lengths=None) -> BitWriter:
-    """A final dynamic block up to the end of its code lengths.  ``items``: code-length symbols, a length 0..12 as an
-    int, a repeat as (16 | 17 | 18, count).  ``cl_lengths``: {symbol: length} of another code-length code (then no
-    items are written: the header is expected to fail before them)."""
+def dynamic_header(items, nlen: int, ndist: int, cl_lengths=None, cl_code=None) -> BitWriter:
+    """A final dynamic block up to the end of its code lengths.  ``items``: code-length symbols, a length as an int
+    (0..12 under the flat code), a repeat as (16 | 17 | 18, count).  ``cl_lengths``: {symbol: length} of another
+    code-length code (then no items are written: the header is expected to fail before them).  ``cl_code``: a complete
+    {symbol: length} code-length code, written and used for the items in place of the flat 4-bit one."""
+    codes = None
+    if cl_code is not None:
+        assert cl_lengths is None and sum(1 << (7 - l) for l in cl_code.values()) == 128 and max(cl_code.values()) <= 7
+        codes = _canonical([cl_code.get(s, 0) for s in range(19)])
     w = BitWriter()
     w.bits(1, 1)
     w.bits(2, 2)
@@ -203,12 +209,16 @@ def dynamic_header(items, nlen: int, ndist: int, cl_lengths=None) -> BitWriter:
     w.bits(ndist - 1, 5)
     w.bits(19 - 4, 4)
     for s in _CL_ORDER:
-        w.bits((cl_lengths.get(s, 0) if cl_lengths is not None else (4 if s in _CL_SYMS else 0)), 3)
+        w.bits(cl_code.get(s, 0) if cl_code is not None else
+               cl_lengths.get(s, 0) if cl_lengths is not None else (4 if s in _CL_SYMS else 0), 3)
     if cl_lengths is not None:
         return w
     for it in items:
         sym, rep = it if isinstance(it, tuple) else (it, None)
-        w.code(_CL_SYMS.index(sym), 4)
+        if codes is None:
+            w.code(_CL_SYMS.index(sym), 4)
+        else:
+            w.code(*codes[sym])
         if sym == 16:
             w.bits(rep - 3, 2)
         elif sym == 17:
@@ -258,6 +268,108 @@ def valid_dynamic():
         assert zlib.decompress(payload, -15) == text, name
         res.append((name, text, wrap(payload, zlib.crc32(text), len(text))))
     return res
+
+
+# A complete code-length code on all 19 symbols with codes of 2 to 7 bits: the lengths 1..6 take 5 bits, 7..13 take 6,
+# 14 and 15 take 7.
+DEEP_CL_CODE = {0: 2, 18: 2, 17: 3, 16: 4, **{s: 5 for s in range(1, 7)}, **{s: 6 for s in range(7, 14)}, 14: 7, 15: 7}
+
+
+class Dynamic:
+    """One final dynamic block under the codes ``lit`` and ``dist`` ({symbol: length}), its header written with
+    ``cl_code``; ``items``: the header's code-length items when they are not to be ``_lengths``'s."""
+
+    def __init__(self, lit, dist, nlen=None, ndist=None, items=None, cl_code=DEEP_CL_CODE):
+        nlen = max(257, max(lit) + 1) if nlen is None else nlen
+        ndist = max(1, max(dist, default=0) + 1) if ndist is None else ndist
+        items = _lengths(nlen, ndist, lit, dist) if items is None else items
+        self.w = dynamic_header(items, nlen, ndist, cl_code=cl_code)
+        self.lit = _canonical([lit.get(s, 0) for s in range(nlen)])
+        self.dist = _canonical([dist.get(s, 0) for s in range(ndist)])
+        self.text = bytearray()
+
+    def lits(self, data: bytes):
+        for b in data:
+            self.w.code(*self.lit[b])
+        self.text += data
+
+    def match(self, length: int, dist: int, len_sym=None):
+        """``len_sym``: the length symbol to use (258 has two: 285, and 284 with all five extra bits set)."""
+        ls = len_sym - 257 if len_sym is not None else \
+            max(k for k in range(29) if LEN_BASE[k] <= length and (k == 28 or length != 258))
+        assert 0 <= length - LEN_BASE[ls] < max(1, 1 << LEN_EXTRA[ls])
+        self.w.code(*self.lit[257 + ls])
+        self.w.bits(length - LEN_BASE[ls], LEN_EXTRA[ls])
+        ds = max(k for k in range(30) if DIST_BASE[k] <= dist)
+        self.w.code(*self.dist[ds])
+        self.w.bits(dist - DIST_BASE[ds], DIST_EXTRA[ds])
+        for _ in range(length):
+            self.text.append(self.text[-dist])
+        return self.lit[257 + ls][1], self.dist[ds][1]
+
+    def end(self):
+        self.w.code(*self.lit[256])
+        return bytes(self.text), self.w.done()
+
+
+def deep_dynamic():
+    """[(name, text, payload)]: hand-made dynamic blocks at the decoder's limits, which zlib accepts."""
+    out = []
+    # literal/length and distance codes of 1 .. 11, 13, 13, 14, 14 and four times 15 bits, the long ones in use
+    lit = {**{97 + k: 1 + k for k in range(11)}, 108: 13, 109: 13, 256: 14, 284: 14, 285: 15, 257: 15, 110: 15, 111: 15}
+    dist = {**{k: 1 + k for k in range(11)}, 11: 13, 12: 13, 13: 14, 14: 14, 26: 15, 27: 15, 28: 15, 29: 15}
+    for with_284 in (False, True):
+        d = Dynamic(lit, dist)
+        d.lits(bytes(np.random.default_rng(41).choice(np.arange(97, 105, dtype=np.uint8), 32768,
+                                                      p=[.5, .25, .125, .0625, .03125, .015625, .0078125, .0078125])))
+        d.lits(bytes([108, 110, 109, 111]))                                  # 13, 15, 13 and 15 bits
+        bits = [d.match(258, 32768), d.match(3, 49 + 15), d.match(3, 97 + 31), d.match(3, 16385 + 8191),
+                d.match(258, 24577), d.match(3, 8193), d.match(3, 12289 + 4095)]
+        assert {b[0] for b in bits} == {15} and {b[1] for b in bits} == {13, 14, 15}
+        if with_284:
+            assert d.match(258, 32768, len_sym=284) == (14, 15)             # 258 = 227 + 31
+        out.append(("codes_of_13_14_15_bits" + ("_and_258_by_284" if with_284 else ""),) + d.end())
+    # the repeat codes at their largest counts: 18 for 138 zeros, 16 for 6 more of the last length, 17 for 10 zeros, and
+    # a 16 that runs from the last two literal/length lengths into the first five distance lengths
+    items = [(18, 138), 3, (16, 6), (17, 10), (18, 101), 4, 5, (16, 6), 1, 2, 4, 5]
+    lit = {**{s: 3 for s in range(138, 145)}, 256: 4, 257: 5, 258: 5}
+    dist = {**{s: 5 for s in range(5)}, 5: 1, 6: 2, 7: 4, 8: 5}
+    d = Dynamic(lit, dist, nlen=259, ndist=9, items=items)
+    d.lits(bytes(range(138, 145)) * 3)
+    for k, (n, far) in enumerate([(3, 1), (4, 2), (3, 3), (4, 4), (3, 5), (4, 7), (3, 9), (4, 13), (3, 17), (4, 21)]):
+        d.match(n, far)
+        d.lits(bytes([138 + k % 7]))
+    out.append(("repeats_at_their_largest",) + d.end())
+    # zlib decides what is a member: an entry it refuses is left out (258 by symbol 284 is the one in question)
+    good = []
+    for name, text, payload in out:
+        try:
+            if zlib.decompress(payload, -15) == text:
+                good.append((name, text, payload))
+                continue
+        except zlib.error:
+            pass
+        assert name.endswith("_and_258_by_284"), name
+    return good
+
+
+def deep_codes():
+    """[(name, text, member)] for the inflate at the code-length limits and the window's edge: the texts of
+    tests/deflate_cases.py made for them, as members of this project's own encoder (both members of each) and of zlib at
+    levels 1, 6 and 9, and the blocks of ``deep_dynamic``.  zlib inflates every one to its text before it is used."""
+    from genefuserust_amd import deflate
+    from tests import deflate_cases as dc
+    out = []
+    for name in ("window_edge", "deep_literals", "deep_distances", "deep_code_lengths", "every_symbol"):
+        text = dc.texts()[name]
+        for k in (0, 1):
+            out.append(("%s_%d_own" % (name, k), text[k * dc.TEXT:(k + 1) * dc.TEXT],
+                        deflate.deflate_member_host(text[k * dc.TEXT:(k + 1) * dc.TEXT])))
+        out += [("%s_zlib_%d" % (name, level), text[:dc.TEXT], member(text[:dc.TEXT], level)) for level in (1, 6, 9)]
+    out += [(name, text, wrap(payload, zlib.crc32(text), len(text))) for name, text, payload in deep_dynamic()]
+    for name, text, m in out:
+        assert zlib.decompress(m[18:-8], -15) == text and zlib.decompress(m, 31) == text, name
+    return out
 
 
 def parts(m: bytes):
@@ -341,6 +453,107 @@ def malformed():
     edit("crc_of_other_text", CRC, member(b"A" * 3000), crc=zlib.crc32(b"B" * 3000))
     edit("payload_with_a_byte_behind", TRAILING, dyn, p + b"\0")
     return out
+
+
+# ---- what a dynamic block is made of ------------------------------------------------------------------------------------
+
+def _canonical(lengths):
+    """{symbol: (code, length)} of the canonical code of ``lengths`` (RFC 1951, 3.2.2)."""
+    code, out = 0, {}
+    for n in range(1, 16):
+        for s, l in enumerate(lengths):
+            if l == n:
+                out[s] = (code, n)
+                code += 1
+        code <<= 1
+    return out
+
+
+def _decode_table(lengths):
+    """For every 15 bits of the stream, first bit least significant: symbol << 4 | code length (0: no code)."""
+    table = np.zeros(1 << 15, dtype=np.int32)
+    for s, (code, n) in _canonical(lengths).items():
+        rev = int(format(code, "0%db" % n)[::-1], 2)
+        table[rev::1 << n] = (s << 4) | n
+    return table.tolist()
+
+
+def tokens_of(payload: bytes):
+    """A raw DEFLATE payload of one final dynamic block, taken apart: (literal/length code lengths [HLIT], distance code
+    lengths [HDIST], code-length code lengths [19], tokens), a token a byte value or (length, distance).  Independent of
+    the decoder under test; ``replay`` turns the tokens back into text."""
+    bits = np.unpackbits(np.frombuffer(payload + b"\0" * 4, dtype=np.uint8), bitorder="little").astype(np.int32)
+    peek = np.zeros(len(bits), dtype=np.int32)
+    for k in range(15):
+        peek[:len(bits) - k] |= bits[k:] << k
+    peek = peek.tolist()
+    assert peek[0] & 7 == 0b101, "one final dynamic block"
+    hlit, hdist, hclen = 257 + (peek[3] & 31), 1 + (peek[8] & 31), 4 + (peek[13] & 15)
+    pos, cl = 17, [0] * 19
+    for k in range(hclen):
+        cl[_CL_ORDER[k]] = peek[pos] & 7
+        pos += 3
+    table, lengths = _decode_table(cl), []
+    while len(lengths) < hlit + hdist:
+        e = table[peek[pos] & 0x7fff]
+        assert e & 15, "bits that are no code of the code-length code"
+        pos += e & 15
+        s = e >> 4
+        if s < 16:
+            lengths.append(s)
+        else:
+            nbits, base = {16: (2, 3), 17: (3, 3), 18: (7, 11)}[s]
+            lengths += [lengths[-1] if s == 16 else 0] * (base + (peek[pos] & ((1 << nbits) - 1)))
+            pos += nbits
+    assert len(lengths) == hlit + hdist
+    lit, dist = lengths[:hlit], lengths[hlit:]
+    lit_table, dist_table, tokens = _decode_table(lit), _decode_table(dist), []
+    while True:
+        e = lit_table[peek[pos] & 0x7fff]
+        assert e & 15, "bits that are no literal/length code"
+        pos += e & 15
+        s = e >> 4
+        if s < 256:
+            tokens.append(s)
+            continue
+        if s == 256:
+            break
+        n = LEN_EXTRA[s - 257]
+        length = LEN_BASE[s - 257] + (peek[pos] & ((1 << n) - 1))
+        pos += n
+        e = dist_table[peek[pos] & 0x7fff]
+        assert e & 15, "bits that are no distance code"
+        pos += e & 15
+        n = DIST_EXTRA[e >> 4]
+        tokens.append((length, DIST_BASE[e >> 4] + (peek[pos] & ((1 << n) - 1))))
+        pos += n
+    assert (pos + 7) // 8 == len(payload), "the block ends in the payload's last byte"
+    return lit, dist, cl, tokens
+
+
+def replay(tokens) -> bytes:
+    out = bytearray()
+    for t in tokens:
+        if isinstance(t, tuple):
+            assert 1 <= t[1] <= len(out)
+            for _ in range(t[0]):
+                out.append(out[-t[1]])
+        else:
+            out.append(t)
+    return bytes(out)
+
+
+def token_symbols(tokens):
+    """(literal/length counts [286] with the end-of-block symbol, distance counts [30]) of a block's tokens."""
+    lit, dist = [0] * 286, [0] * 30
+    lit[256] = 1
+    for t in tokens:
+        if isinstance(t, tuple):
+            lit[257 + (28 if t[0] == 258 else max(k for k in range(28) if LEN_BASE[k] <= t[0]))] += 1
+            dist[max(k for k in range(30) if DIST_BASE[k] <= t[1])] += 1
+        else:
+            lit[t] += 1
+    return lit, dist
 
 
 # ---- the walk ---------------------------------------------------------------------------------------------------------------

@@ -5,6 +5,9 @@
 //
 // One job a line, one line of answers each:
 //     member <text file> <member file>    the member of the file's text (1 .. 65280 bytes): "<size> <kind>"
+//     plan <file of 316 counts>           gf_df_order on both alphabets (286 literal/length counts, then 30 distance
+//                                         counts), then gf_df_plan, in a heap block of exactly one GfDfPlan:
+//                                         "<lens[316]> <cl_lens[19]> <cl_freq[19]> <hlit> <hdist> <bits>"
 //     len <length - 3>                    "<index> <extra bits> <value>" of the length symbol
 //     dist <distance - 1>                 "<symbol> <extra bits> <value>" of the distance symbol
 //     minlen <distance>                   from how many bytes on a match at this distance is taken
@@ -67,6 +70,25 @@ int main(int argc, char** argv) {
       delete[] out;
       delete[] units;
       delete[] table;
+    } else if (what == "plan") {
+      std::string from;
+      in >> from;
+      std::ifstream counts(from);
+      GfDfPlan* P = new GfDfPlan;
+      uint32_t got = 0;
+      while (got < GF_DF_NSYM && (counts >> P->freq[got])) got++;
+      if (got != GF_DF_NSYM) {
+        fprintf(stderr, "%s: %u counts, not %u\n", from.c_str(), got, GF_DF_NSYM);
+        return 2;
+      }
+      gf_df_order(P->freq, GF_DF_NLIT, P->order);
+      gf_df_order(P->freq + GF_DF_NLIT, GF_DF_NDIST, P->order + GF_DF_NLIT);
+      gf_df_plan(*P);
+      for (uint32_t s = 0; s < GF_DF_NSYM; s++) answers << (uint32_t)P->lens[s] << " ";
+      for (uint32_t k = 0; k < GF_DF_NCL; k++) answers << (uint32_t)P->cl_lens[k] << " ";
+      for (uint32_t k = 0; k < GF_DF_NCL; k++) answers << P->cl_freq[k] << " ";
+      answers << P->hlit << " " << P->hdist << " " << P->bits << "\n";
+      delete P;
     } else if (what == "len" || what == "dist") {
       uint32_t x, a, b, c;
       in >> x;

@@ -19,6 +19,7 @@ from tests.test_read_write_gpu import CHUNK, _all_steps, _read, _texts, files   
 pytestmark = pytest.mark.gpu
 GUARD, JUNK = 64, 0xA5
 T = dc.TEXT
+NEW_TEXTS = ("window_edge", "deep_literals", "deep_distances", "deep_code_lengths", "every_symbol")
 
 
 @functools.lru_cache(maxsize=None)
@@ -113,7 +114,7 @@ def test_the_true_length_is_read_on_the_device(gpu_device):
 
 
 def test_two_runs_give_the_same_bytes(gpu_device):
-    for name in ("fastq", "chained_258", "motif_32768"):
+    for name in ("fastq", "chained_258", "motif_32768") + NEW_TEXTS:
         text = dc.texts()[name]
         assert device_deflate(text, lead=3) == device_deflate(text, lead=3)
 
@@ -142,6 +143,27 @@ def test_the_binding_and_the_device_inflate_read_it_back(gpu_device):
         assert back[:true_len].cpu().numpy().tobytes() == text[:true_len] and set(back[true_len:].cpu().tolist()) == {JUNK}
     out, member_off, totals = df.deflate_device(torch.empty(0, dtype=torch.uint8, device="cuda"))
     assert member_off.cpu().tolist() == [0] and totals.cpu().tolist() == [0] * 5
+
+
+def test_the_texts_at_the_limits_come_back_through_the_device_inflate(gpu_device):
+    """The texts made for the code-length limits and the window's edge (tests/test_deflate_core.py pins what each
+    reaches), whole: three members each from the device deflate, the host model's bytes, and the device inflate gives
+    the text back, every status 0."""
+    import torch
+    from genefuserust_amd import bgzf
+    for name in NEW_TEXTS:
+        text = dc.texts()[name]
+        out, member_off, totals = df.deflate_device(torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda())
+        t = totals.cpu().tolist()
+        assert t[:2] == [3, len(text)] and t[3:] == [1, 2], name          # two dynamic members and the single byte, stored
+        comp = out[:t[2]].cpu().numpy()
+        assert comp.tobytes() == b"".join(host_members(text)), name
+        walk = bgzf.walk_blocks(comp)
+        assert (walk.members, walk.comp_bytes, walk.text_bytes, walk.why) == (3, t[2], len(text), bm.WALK_END)
+        back = torch.full((len(text) + 16,), JUNK, dtype=torch.uint8, device="cuda")
+        status, totals = bgzf.inflate_device(out[:t[2]], torch.from_numpy(walk.table.copy()).cuda(), back)
+        assert status.cpu().tolist() == [0] * 3 and totals.cpu().tolist() == [3, -1, 0, len(text)], name
+        assert back[:len(text)].cpu().numpy().tobytes() == text and set(back[len(text):].cpu().tolist()) == {JUNK}, name
 
 
 def test_host_memory_is_refused(gpu_device):

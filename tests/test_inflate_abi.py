@@ -60,6 +60,20 @@ def test_every_kind_against_zlib(gpu_device, good):
         check(good[:5], text_gap=0, comp_gap=0, text_base=base)
 
 
+def test_codes_at_their_limits(gpu_device):
+    """``deep_codes`` (the host build has passed them in tests/test_inflate_core.py): codes of 13 to 15 bits, a
+    code-length code of 5 to 7 bits, the largest repeats, length 258 both ways and distance 32768, by hand, by this
+    project's encoder and by zlib: every text back, status 0, at odd offsets between sentinels."""
+    cases = bm.deep_codes()
+    for name, text, m in cases:
+        assert gzip.decompress(m) == text, name
+    check(cases)
+    hand = [c for c in cases if not c[0].endswith("_own") and "_zlib_" not in c[0]]
+    assert len(hand) == 3
+    for base in (0, 1, 7, 15):
+        check(hand + cases[:2], text_gap=0, comp_gap=0, text_base=base)
+
+
 @pytest.mark.parametrize("count", [1, 2, 513])
 def test_member_counts(gpu_device, good, count):
     """One, two, one more than the grid holds (the members stride)."""

@@ -78,6 +78,25 @@ def test_members_zlib_cannot_emit(program, tmp_path):
     check_good(program, tmp_path, bm.hand_assembled() + bm.valid_dynamic())
 
 
+def test_codes_at_their_limits(program, tmp_path):
+    """``deep_codes``: literal/length and distance codes of 13, 14 and 15 bits in use, a code-length code of 5 to 7
+    bits, the repeat codes at their largest counts and across the two alphabets, length 258 both ways, distance 32768
+    under a 15-bit code — by hand, by this project's encoder on the texts made for its limits, and by zlib on the same
+    texts.  What the hand-made blocks hold is read off them first, by a parser of its own."""
+    lit, dist, cl, tokens = bm.tokens_of(bm.deep_dynamic()[-2][2])
+    assert {13, 14, 15} <= set(lit) and {13, 14, 15} <= set(dist) and {2, 3, 4, 5, 6, 7} == set(cl)
+    assert tokens[-1] == (258, 32768) and (258, 32768) in tokens[:-1] and (3, 16385 + 8191) in tokens
+    lit, dist, cl, tokens = bm.tokens_of(bm.deep_dynamic()[-1][2])
+    assert lit[138:145] == [3] * 7 and lit[145:256] == [0] * 111 and lit[257:] + dist[:5] == [5] * 7
+    cases = bm.deep_codes()
+    names = [c[0] for c in cases]
+    assert len(cases) == 28 and "codes_of_13_14_15_bits_and_258_by_284" in names      # zlib takes 258 = 227 + 31
+    deep = {c[0]: bm.tokens_of(bm.parts(c[2])[0]) for c in cases if c[0].endswith("_own")}
+    assert max(deep["deep_literals_0_own"][0]) == 15 and max(deep["deep_distances_1_own"][1]) == 15
+    assert max(deep["deep_code_lengths_0_own"][2]) == 7 and (201, 32768) in deep["window_edge_0_own"][3]
+    check_good(program, tmp_path, cases)
+
+
 def test_malformed_members(program, tmp_path):
     bad = bm.malformed()
     good_text = bm.fastq_text(5000, seed=8)
